@@ -7,8 +7,14 @@ sized to 288 GB HBM". One process per GPU (torch.distributed.run), halo
 exchange GPU-direct over RCCL/xGMI overlapped with the interior kernel.
 
     python bench.py                                   # 1 GPU, 1000 steps, 10 warmup
+    python bench.py --full                            # + the checks and side measurements
+    python bench.py --dump-outputs DIR                # + the timed field as DIR/field.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \\
-        --master-addr 127.0.0.1 --master-port 29600 bench.py --gpus 8
+        --master-addr 127.0.0.1 --master-port 29600 bench.py --gpus 8 --full
+
+A plain run sets up, warms up, times the steps and prints the record (the
+keys of the --full measurements are null). Everything else below runs only
+with ``--full``; asking for one of its options without it is an error.
 
 T_eff per GPU follows the reference exactly (scripts/diffusion_2D_perf.jl:55-58):
 A_eff = 3*nx*ny*8 B per step on the LOCAL tile (halo included), divided by the
@@ -17,8 +23,8 @@ are timed between barrier+device-sync pairs; the step time is the MAX over
 ranks; ``value`` is the whole-job aggregate = N x per-GPU T_eff (weak scaling:
 the local tile is the same for every N). Data: synthetic random-init field.
 
-The run validates itself and says which rank is slow (VERDICT r1 item 1, r2
-items 1-3):
+A ``--full`` run validates itself and says which rank is slow (VERDICT r1 item
+1, r2 items 1-3):
 * preflight, before the HBM-sized tile is allocated: the GPU-direct ring
   send/recv of the reference's smoke test (scripts/rocmaware_test_selectdevice.jl:
   16-23) over the halo transport (RCCL; RCCL to self on one GPU) and a tiny
@@ -58,6 +64,15 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 METRIC = "T_eff (GB/s) + weak-scaling eff., 2D diffusion 1000 steps at 1/2/4/8 MI355X"
+
+
+# the options of the --full measurements and checks, with the value that
+# switches each off in a plain run
+FULL_ONLY = {"preflight": 0, "link_probe": 0, "check": 0, "check_nx": 0, "check_self_rccl": 0,
+             "window_check": 0, "full_field_check": 0, "drift_steps": 0, "single_step_steps": 0,
+             "canonical_steps": 0, "solo_steps": 0}
+DUMP_MAX_BYTES = 32 << 20
+DUMP_SEED = 20240611
 
 
 def parse(argv=None):
@@ -141,7 +156,47 @@ def parse(argv=None):
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: the same driver on the C++ CPU twins over gloo (tests of the "
                          "multi-rank bench path; needs --nx; not a benchmark)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed run: the preflight and link probe, the full-field, "
+                         "window, drift and halo checks, the solo re-time with the weak-scaling "
+                         "attribution, and the canonical / one-step kernel timings. Off: the run "
+                         "sets up, warms up, times --steps steps and prints the record")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write this rank's field as DIR/field.npy "
+                         "(DIR/field_rank<r>.npy with several ranks), float64; a field above "
+                         f"{DUMP_MAX_BYTES >> 20} MiB is written as a fixed seeded sample of its cells")
+    a = ap.parse_args(argv)
+    if not a.full:
+        # a plain run does none of the side measurements and checks: asking for
+        # one without --full is an error, never silently ignored
+        asked = [f"--{k.replace('_', '-')}" for k in FULL_ONLY if getattr(a, k) != ap.get_default(k)]
+        if asked:
+            ap.error(f"{', '.join(asked)}: needs --full (a plain run only times the steps)")
+        for k in FULL_ONLY:
+            setattr(a, k, FULL_ONLY[k])
+    return a
+
+
+def dump_outputs(field, out_dir: str, world: int, rank: int) -> dict:
+    """What the timed path computed in its last step: this rank's field, whole
+    when it fits DUMP_MAX_BYTES, else the cells at fixed seeded (row, column)
+    positions (the same positions for the same tile shape, whatever the build)."""
+    import numpy as np
+    import torch
+
+    ny, nx = field.shape
+    n = DUMP_MAX_BYTES // 8 // world  # all ranks together stay within DUMP_MAX_BYTES
+    if ny * nx <= n:
+        vals, sampled = field.detach().cpu().numpy(), False
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        iy = torch.from_numpy(rng.integers(0, ny, size=n)).to(field.device)
+        ix = torch.from_numpy(rng.integers(0, nx, size=n)).to(field.device)
+        vals, sampled = field.detach()[iy, ix].cpu().numpy(), True
+    os.makedirs(out_dir, exist_ok=True)
+    name = "field.npy" if world == 1 else f"field_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), np.ascontiguousarray(vals, dtype=np.float64))
+    return {"file": name, "shape": list(vals.shape), "sampled": sampled}
 
 
 def auto_tile(frac: float, cap: int) -> int:
@@ -395,6 +450,8 @@ def run(a, world: int, rank: int) -> int:
         snap = snapshot_windows(model) if a.window_check and a.variant != "kp" else None
         timings = summarize_timings(model.pass_timings(), exchange=nbrs)
         model.enable_pass_timing(False)
+        # the timed field, before the side measurements step it further
+        dumped = dump_outputs(model.field, a.dump_outputs, world, rank) if a.dump_outputs else None
         ex = getattr(model, "executor", None)
         # passes of the warmup + timed steps and how many ran as frame-first fused launches
         # (RMA_EXEC_FUSED: with neighbours and >= 2 waves of tasks per pass)
@@ -546,10 +603,11 @@ def run(a, world: int, rank: int) -> int:
         fast_plan = bool(fast_used)
         n1key = _n1_key(nx, ny, a.steps, a.warmup, K, fast_plan, a.variant)
         n1 = None
-        if world == 1 and not nbrs:
+        # the N = 1 record belongs to the weak-scaling attribution (--full)
+        if a.full and world == 1 and not nbrs:
             save_n1(n1key, t_it * 1e3, bus)
             n1 = {"ms_per_step": t_it * 1e3}
-        elif world > 1:
+        elif a.full and world > 1:
             n1 = load_n1(n1key)
         n1_ms = n1["ms_per_step"] if n1 else None
         isos = [d["solo_iso_ms_per_step"] for d in ranks_detail if d["solo_iso_ms_per_step"]]
@@ -623,6 +681,8 @@ def run(a, world: int, rank: int) -> int:
             "executor_passes": exec_passes,
             "setup_s": round(setup_s, 3),
             "full_field_check": ffc,
+            "full": bool(a.full),
+            "dump_outputs": dumped,
         })
 
         # --- correctness of this run's code paths (bounded; any failure fails all)

@@ -20,8 +20,8 @@ step() {  # name timeout cmd...
 }
 step pytest_gpu 700 python -m pytest tests -m gpu -x -q &&
 step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" &&
-step bench 400 python bench.py --json-out "$OUT/bench.json" &&
+step bench 400 python bench.py --full --json-out "$OUT/bench.json" &&
 step baseline_presets 400 python bench/baseline_configs.py --max-gpus 1 --out "$OUT/baseline_configs.json" &&
 (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
-    -d "$R/$OUT/trace" -o run -- python3 "$R/bench.py" --steps 120 --single-step-steps 24 \
+    -d "$R/$OUT/trace" -o run -- python3 "$R/bench.py" --full --steps 120 --single-step-steps 24 \
     > "$R/$OUT/trace.log" 2>&1; rc=$?; echo "== trace rc=$rc"; exit $rc)

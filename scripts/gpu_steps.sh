@@ -56,10 +56,10 @@ for s in "$@"; do
              --pipe5 20 --kinds piper:20,piper:24 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepr2.json" || exit 1 ;;
     bench20_pipe|bench20_piper|bench20_pipe5) v=${s#bench20_}
-             RMA_PIPE_FAST=$v step "$s" 300 python bench.py --gpus 1 --steps 20 --warmup 5 \
+             RMA_PIPE_FAST=$v step "$s" 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 \
              --json-out "$OUT/$s.json" || exit 1 ;;
     bench1000_pipe|bench1000_piper) v=${s#bench1000_}
-             RMA_PIPE_FAST=$v step "$s" 300 python bench.py --json-out "$OUT/$s.json" || exit 1 ;;
+             RMA_PIPE_FAST=$v step "$s" 300 python bench.py --full --json-out "$OUT/$s.json" || exit 1 ;;
     sweepr3) step sweepr3 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe 17,18,19,20,24 \
              --kinds piper:17,piper:18,piper:19,piper:20 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepr3.json" || exit 1 ;;
@@ -81,7 +81,7 @@ for s in "$@"; do
              --kinds piper:20,piper:20:2048,piper:20:4096,piper:20:6144,piper:24,piper:24:2048,piper:24:4096,piper:24:6144 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepc.json" || exit 1 ;;
     prof20) prof prof20 300 --kernel-trace --stats -d "$R/$OUT/prof20" -o run -- python3 \
-             "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --json-out "$R/$OUT/prof20.json" || exit 1 ;;
+             "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 --json-out "$R/$OUT/prof20.json" || exit 1 ;;
     sweeplo) step sweeplo 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe 10,12,14,16,17,18 \
              --kinds piper:10,piper:12,piper:14,piper:16,piper:17,piper:18 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweeplo.json" && \
@@ -98,7 +98,7 @@ for s in "$@"; do
              NCCL_MIN_P2P_NCHANNELS=$c NCCL_MAX_P2P_NCHANNELS=$c step "$s" 300 python \
              bench/rccl_self_overhead.py --n 4096 --K 1 --variants perf_hide --steps 400 --pattern opop \
              --out "$OUT/$s.json" || exit 1 ;;
-    bench6000) step bench6000 400 python bench.py --steps 6000 --warmup 24 \
+    bench6000) step bench6000 400 python bench.py --full --steps 6000 --warmup 24 \
              --json-out "$OUT/bench6000.json" || exit 1 ;;
     pmc_bytes) prof pmc_fetch 300 --pmc FETCH_SIZE SQ_WAVES GRBM_GUI_ACTIVE \
              --output-format csv -d "$R/$OUT/pmc_fetch" -o run -- python3 "$R/bench/pass_sweep.py" \
@@ -261,11 +261,11 @@ for s in "$@"; do
     presets_shared) step presets_shared 600 python bench/baseline_configs.py --shared-gpu --nt 120 \
              --out "$OUT/baseline_configs_shared.json" || exit 1 ;;
     rehearse) for n in 2 4 8; do
-               step "rehearse$n" 400 python bench.py --gpus $n --shared-gpu-test --shared-gpu-transport rccl \
+               step "rehearse$n" 400 python bench.py --full --gpus $n --shared-gpu-test --shared-gpu-transport rccl \
                  --nx 4096 --steps 96 --warmup 4 --json-out "$OUT/rehearse$n.json" || exit 1
              done ;;
     rehearse_fused) for n in 2 4 8; do
-               step "rehearse_fused$n" 400 python bench.py --gpus $n --shared-gpu-test --shared-gpu-transport rccl \
+               step "rehearse_fused$n" 400 python bench.py --full --gpus $n --shared-gpu-test --shared-gpu-transport rccl \
                  --nx 8192 --steps 96 --warmup 4 --json-out "$OUT/rehearse_fused$n.json" || exit 1
              done ;;
     tests_ipc5) step tests_ipc5 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread \
@@ -319,7 +319,7 @@ for s in "$@"; do
                  bench/ipc_transport_probe.py --transport $1 --n $2 --K $3 --steps $4 $5 || exit 1
              done ;;
     bench_small) for n in 16384 8192 4096; do
-               step "bench1000_$n" 300 python bench.py --nx $n --steps 1000 --json-out "$OUT/bench1000_$n.json" || exit 1
+               step "bench1000_$n" 300 python bench.py --full --nx $n --steps 1000 --json-out "$OUT/bench1000_$n.json" || exit 1
              done ;;
     tests_halo) step tests_halo 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread \
              tests/test_halo_gpu.py -p no:cacheprovider || exit 1 ;;
@@ -346,9 +346,9 @@ for s in "$@"; do
              "tests/test_temporal_gpu.py::test_headline_kernels_beyond_2e31_cells" \
              -p no:cacheprovider || exit 1 ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench20) step bench20 300 python bench.py --gpus 1 --steps 20 --warmup 5 \
+    bench20) step bench20 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 \
              --json-out "$OUT/bench20.json" || exit 1 ;;
-    bench1000) step bench1000 300 python bench.py --json-out "$OUT/bench1000.json" || exit 1 ;;
+    bench1000) step bench1000 300 python bench.py --full --json-out "$OUT/bench1000.json" || exit 1 ;;
     nbr_x|nbr_y|nbr_xy) d=${s#nbr_}
              step "$s" 400 python bench/rccl_self_overhead.py --K 24 --periodic "$d" --steps 320 \
              --pattern opop --out "$OUT/$s.json" || exit 1 ;;
@@ -480,7 +480,7 @@ for s in "$@"; do
     rccl_graph) step rccl_graph 500 python bench/rccl_graph_probe.py --n 4096 --steps 400 \
              --out "$OUT/rccl_graph.json" || exit 1 ;;
     trace20) prof trace20 300 --kernel-trace --stats --output-format csv -d "$R/$OUT/trace20" \
-             -o run -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 || exit 1 ;;
+             -o run -- python3 "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 || exit 1 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
 done

@@ -81,7 +81,7 @@ def test_bench_cpu_records_full_field_check(tmp_path, corrupt):
         env["RMA_DIAG"] = f"bench_field_corrupt={corrupt}"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu",
                         "--nx", "130", "--steps", "12", "--warmup", "2",
-                        "--single-step-steps", "2"], capture_output=True, text=True,
+                        "--single-step-steps", "2", "--full"], capture_output=True, text=True,
                        timeout=600, cwd=str(tmp_path), env=env)
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     ffc = rec["config"]["full_field_check"]
@@ -144,3 +144,83 @@ def test_rccl_debug_env_never_uses_stdout(tmp_path):
     old = _os.environ.get("NCCL_DEBUG_FILE")
     assert P.read_own_rccl_log(env["NCCL_DEBUG_FILE"]) == SOCKET_LOG
     assert old == _os.environ.get("NCCL_DEBUG_FILE")
+
+
+def _plain_bench(tmp_path, *args):
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    env.pop("RMA_DIAG", None)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu",
+                           *args], capture_output=True, text=True, timeout=300,
+                          cwd=str(tmp_path), env=env)
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_timed_field(tmp_path):
+    """Without --full: the record carries the headline keys, none of the side
+    measurements ran, and --dump-outputs holds the field after warmup + steps
+    steps, bitwise equal to the same model stepped directly and identical
+    from run to run."""
+    import numpy as np
+
+    from rocm_mpi_amd.models import Diffusion2D, DiffusionConfig
+
+    fields = []
+    for name in ("a", "b"):
+        r = _plain_bench(tmp_path, "--nx", "131", "--ny", "97", "--steps", "12", "--warmup", "3",
+                         "--temporal", "6", "--dump-outputs", str(tmp_path / name))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        fields.append(np.load(tmp_path / name / "field.npy"))
+    d = json.loads(lines[0])
+    assert d["steps"] == 12 and d["warmup"] == 3 and d["ms_per_step"] > 0
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "fp64"
+    assert abs(d["value"] - 3 * 131 * 97 * 8 / 1e9 / (d["ms_per_step"] / 1e3)) <= 1e-3 * d["value"] + 0.01
+    c = d["config"]
+    assert c["full"] is False and sum(c["passes_timed"]) == 12
+    for k in ("preflight", "full_field_check", "headline_window_check", "halo_check",
+              "drift_check", "solo_ms_per_step", "teff_single_step_kernel_GBps",
+              "teff_bitwise_kstep_GBps"):
+        assert c.get(k) is None, k
+    assert c["dump_outputs"] == {"file": "field.npy", "shape": [97, 131], "sampled": False}
+    assert fields[0].dtype == np.float64 and np.array_equal(fields[0], fields[1])
+    m = Diffusion2D(DiffusionConfig(variant="perf_hide", nx=131, ny=97, nt=15, warmup=3,
+                                    device="cpu", quiet=True, init="random", temporal=6,
+                                    fast_math=True))
+    m.step(3)
+    m.step(12)
+    assert np.array_equal(fields[0], m.field.numpy())
+    m.close()
+
+
+def test_bench_dump_outputs_samples_a_large_field(tmp_path, monkeypatch):
+    """A field above the size limit is written as the cells at fixed seeded
+    positions: the same positions on every call, each value a cell of the
+    field."""
+    import numpy as np
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 500)
+    f = torch.arange(61 * 43, dtype=torch.float64).reshape(61, 43)
+    infos = [bench.dump_outputs(f, str(tmp_path / n), 1, 0) for n in ("a", "b")]
+    assert infos[0] == {"file": "field.npy", "shape": [500], "sampled": True}
+    a, b = (np.load(tmp_path / n / "field.npy") for n in ("a", "b"))
+    assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.all((a >= 0) & (a < 61 * 43) & (a == np.round(a))) and len(set(a.tolist())) > 250
+    # two ranks share the limit and write one file each
+    i1 = bench.dump_outputs(f, str(tmp_path / "w2"), 2, 1)
+    assert i1 == {"file": "field_rank1.npy", "shape": [250], "sampled": True}
+
+
+@pytest.mark.parametrize("opt", [["--check", "1"], ["--solo-steps", "4"],
+                                 ["--single-step-steps", "8"], ["--preflight", "0"]])
+def test_bench_refuses_a_full_only_option_in_a_plain_run(opt):
+    """Asking for a --full measurement (or switching one off) without --full is
+    an error, not a silently ignored option."""
+    import bench
+
+    with pytest.raises(SystemExit) as ei:
+        bench.parse(["--nx", "64", *opt])
+    assert ei.value.code == 2
+    a = bench.parse(["--nx", "64", "--full", *opt])
+    assert a.full and getattr(a, opt[0][2:].replace("-", "_")) == int(opt[1])

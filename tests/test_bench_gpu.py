@@ -12,11 +12,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def bench(*args, timeout=300):
+def bench(*args, timeout=300, full=True):
     from helpers import free_port
 
     env = dict(os.environ, MASTER_PORT=str(free_port()))  # multi-rank runs self-launch
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args],
+    # the checks and side measurements these tests assert on run with --full
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args,
+                        *(["--full"] if full else [])],
                        capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -145,3 +147,30 @@ def test_bench_rehearsal_of_the_scaling_run_over_rccl(gpus, dims):
     assert all(len(r["timed"]) == 3 * len(r["peers"]) and r["peers"] for r in lk["ranks"])
     assert c["scaling_point"] is False and c["full_field_check"]["ok"]
     assert "socket" in c["parallelism"] or "NET" in c["parallelism"] or "socket" in str(lk)
+
+
+def test_bench_plain_run_dumps_the_timed_field(tmp_path):
+    """The plain command shape (no --full): only the timed steps run, and
+    --dump-outputs holds the timed field, bitwise equal to the CPU twin after
+    warmup + steps steps of the same plan (odd tile, passes of 24 and less)."""
+    import numpy as np
+
+    from rocm_mpi_amd.models import Diffusion2D, DiffusionConfig
+
+    d = bench("--gpus", "1", "--steps", "30", "--warmup", "3", "--nx", "1031", "--ny", "773",
+              "--dump-outputs", str(tmp_path), full=False)
+    c = d["config"]
+    assert d["steps"] == 30 and d["ms_per_step"] > 0 and c["full"] is False
+    assert sum(c["passes_timed"]) == 30 and c["fast_math"] is True
+    for k in ("preflight", "full_field_check", "headline_window_check", "halo_check",
+              "drift_check", "solo_ms_per_step", "teff_single_step_kernel_GBps"):
+        assert c.get(k) is None, k
+    got = np.load(tmp_path / "field.npy")
+    assert got.dtype == np.float64 and got.shape == (773, 1031)
+    m = Diffusion2D(DiffusionConfig(variant="perf_hide", nx=1031, ny=773, nt=33, warmup=3,
+                                    device="cpu", quiet=True, init="random", temporal=24,
+                                    fast_math=True))
+    m.step(3)
+    m.step(30)
+    assert np.array_equal(got, m.field.numpy())
+    m.close()

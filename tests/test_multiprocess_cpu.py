@@ -95,7 +95,7 @@ def test_bench_driver_contract_multirank(tmp_path, world, extra):
            f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(root, "bench.py"),
            "--gpus", str(world), "--steps", "20", "--warmup", "3", "--device", "cpu",
-           "--nx", str(nx), "--single-step-steps", "4", *extra]
+           "--nx", str(nx), "--single-step-steps", "4", "--full", *extra]
     K = int(extra[1])
     # the N = 1 record of this tile class, as the driver's N = 1 run of the
     # same sweep leaves it (bench.py save_n1): e_box is then defined. The
@@ -216,7 +216,7 @@ def test_bench_window_check_detects_a_wrong_cell(tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "2",
            "--device", "cpu", "--nx", "64", "--temporal", "4", "--dims", "2,1",
-           "--single-step-steps", "0", "--check", "0", "--drift-steps", "0"]
+           "--single-step-steps", "0", "--check", "0", "--drift-steps", "0", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1",
                RMA_DIAG=f"bench_window_corrupt,bench_n1_cache={tmp_path / 'none.json'}")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
@@ -246,7 +246,7 @@ def test_bench_halo_check_detects_a_wrong_tile(tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
            "--device", "cpu", "--nx", "64", "--single-step-steps", "0", "--temporal", "4",
-           "--solo-steps", "0"]
+           "--solo-steps", "0", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", RMA_DIAG="bench_check_corrupt")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
                        env=env)
@@ -278,7 +278,7 @@ def test_bench_check_exception_fails_every_rank(tmp_path, where, tmo):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
            "--device", "cpu", "--nx", "64", "--single-step-steps", "0", "--temporal", "4",
-           "--solo-steps", "0", "--drift-steps", "0", "--check-timeout", str(tmo)]
+           "--solo-steps", "0", "--drift-steps", "0", "--check-timeout", str(tmo), "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1",
                RMA_DIAG=f"bench_check_raise={where},bench_rc_dir={rcdir}")
     t0 = time.time()
@@ -310,7 +310,7 @@ def test_bench_preflight_runs_before_the_tile(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "30",
                         "--warmup", "3", "--device", "cpu", "--nx", "80", "--temporal", "6",
-                        "--single-step-steps", "0"], capture_output=True, text=True,
+                        "--single-step-steps", "0", "--full"], capture_output=True, text=True,
                        timeout=300, cwd=str(tmp_path), env=dict(os.environ, OMP_NUM_THREADS="2"))
     assert r.returncode == 0, r.stderr[-3000:]
     c = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["config"]
