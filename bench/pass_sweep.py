@@ -51,7 +51,7 @@ def main(argv=None):
                     "(needs n %% 5 == 0)")
     ap.add_argument("--chunks5", default="", help="pipe5 K:c1/c2/..., chunk-row variants")
     ap.add_argument("--kinds", default="", help="other K-step kernels by name, kernel:K[:chunk],"
-                    "... (e.g. piper:24,piper:24:4096,pipe_diag1:24; 4 cells per lane)")
+                    "... (e.g. piper:24,piper:24:4096,piper_nosb:20; 4 cells per lane)")
     ap.add_argument("--coef-dims", default="1,1",
                     help="coefficients of this process grid at overlap 48 (K = 24): dx = "
                          "10/(dimx(n-48)+48), dy = 10/(dimy(n-48)+48); 1,1 = dx = dy (ry = 1), "
@@ -97,12 +97,7 @@ def main(argv=None):
         # the executor's rows per task for this kernel and depth
         if c or a.chunk:
             return c or a.chunk
-        if kind in ("pipe", "pipe2", "pipeb", "pipe5", "piper", "pipe_diag1", "piper6", "piper7",
-                    "piper_u3", "piper_iso", "piper_diag_s0", "piper_w1", "piper_mask",
-                    "piper_mask_ctl", "piper_nosb",
-                    "piper_rot", "piper_diag_hb", "piper_u6s",
-                    "piper_sp", "piper_sp2", "piper_prio", "piper_prio_nr", "piper2",
-                    "piper_rot2"):
+        if kind in ("pipe", "pipe2", "pipe5", "piper", "piper_nosb", "piper2"):
             return N.pipe_chunk_rows(K, n, False) or N.default_chunk_k(max(K, 3), n)
         if kind == "pipec":
             return N.pipe_chunk_rows(K, n, True) or N.default_chunk_k(max(K, 3), n)
@@ -159,8 +154,8 @@ def main(argv=None):
             ops.stencilk_step(K, T2, T, iCp, coef, rect, tn)
         else:
             vec = 2 if kind in ("lds_dpp", "fast5") else 5 if kind == "pipe5" else 4
-            # "<kernel>2": two column waves per stage (pipe2, piper2, piper_rot2)
-            cols2 = kind in ("pipe2", "piper2", "piper_rot2")
+            # "<kernel>2": two column waves per stage (pipe2, piper2)
+            cols2 = kind in ("pipe2", "piper2")
             kern = "pipe" if kind in ("pipe2", "pipe5") else kind[:-1] if cols2 else kind
             tn = ops.StencilTuning(chunk_rows=chunk(K, c, kind), kernel=kern,
                                    vec=vec, xcd_remap=1, stages=S, cols=2 if cols2 else 0)

@@ -56,7 +56,7 @@ if which == "cols":  # piper with 1 vs 2 column waves per stage (VERDICT r5 next
     K = int(os.environ.get("RMA_PROBE_K", "20"))
     ch = nat.pipe_chunk_rows(K, n, False) or nat.default_chunk_k(K, n)
     rect = [ops.interior_rect(n, n)]
-    for kern, cols in (("piper", 1), ("piper", 2), ("piper_rot", 2)):
+    for kern, cols in (("piper", 1), ("piper", 2)):
         for _ in range(reps):
             ops.stencilk_step(K, T2, T, iCp, c, rect,
                               ops.StencilTuning(chunk_rows=ch, xcd_remap=1, kernel=kern, vec=4,

@@ -7,7 +7,7 @@ tile while a thread samples ``rocm-smi --showpower --showclocks`` once per
 second, and reports the median pass time with the median power and clock of
 the samples taken inside that window. Prints one JSON document.
 
-    python bench/power_probe.py --configs pipe:16,pipe:20,pipe:24,pipeb:20 --seconds 6
+    python bench/power_probe.py --configs pipe:16,pipe:20,pipe:24,piper:20 --seconds 6
     python bench/power_probe.py --configs pipe:24:iso,pipe:24:aniso,pipe:24:pow2
 
 A third field picks the coefficients: iso (dx = dy = 10/n: ry = (dx/dy)^2 = 1, the
@@ -61,7 +61,7 @@ def smi_power_cap() -> float | None:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=0)
-    ap.add_argument("--configs", default="march:1,pipe:16,pipe:20,pipe:24,pipeb:16,pipeb:20")
+    ap.add_argument("--configs", default="march:1,pipe:16,pipe:20,pipe:24")
     ap.add_argument("--seconds", type=float, default=6.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)

@@ -166,18 +166,10 @@ PYBIND11_MODULE(_C, m) {
           stencilk_rects_gpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny,
                              r.data(), (int)r.size(), to_coef(coef), tn, S(stream));
         else {
-          // the CPU twin of the kernel's arithmetic: fast5 (kernels 5-9, 11, 12), the
-          // split fast-math form (14, 15) or canonical
-          const bool f5 = (kernel >= 5 && kernel <= 9) || kernel == 11 || kernel == 12 ||
-                          kernel == 16 || kernel == 17 || kernel == 19 ||
-                          kernel == 20 || kernel == 21 || kernel == 22 || kernel == 23 ||
-                          kernel == 25 || kernel == 26 || kernel == 27;
-          const bool f6 = kernel == 14 || kernel == 15;
+          // the CPU twin of the kernel's arithmetic: fast5 (kernels 5-9, 12, 22) or canonical
+          const bool f5 = (kernel >= 5 && kernel <= 9) || kernel == 12 || kernel == 22;
           py::gil_scoped_release nogil;
-          if (f6)
-            stencilk6_rects_cpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx,
-                                ny, r.data(), (int)r.size(), to_coef(coef));
-          else if (f5)
+          if (f5)
             stencilk5_rects_cpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx,
                                 ny, r.data(), (int)r.size(), to_coef(coef));
           else

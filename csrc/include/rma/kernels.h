@@ -104,12 +104,14 @@ void stencilk_rects_cpu(int K, double* T2, const double* T, const double* iCp, i
 // factor, 5 ops). 4 and 5 are not bitwise equal to the canonical update.
 // fast5_ok: kernel 5 divides by lam/dx^2, so it needs lam != 0.
 bool fast5_ok(const StencilCoef& c);
-//   9 pipe  (fast5 arithmetic) / 10 pipec (canonical) / 11 pipeb (fast5, lane
-//     moves by ds_bpermute; K = 16, 20, 24 only): stage-pipelined strips
+//   9 pipe  (fast5 arithmetic) / 10 pipec (canonical): stage-pipelined strips
 //     for ANY K in 1..kPipeMaxK (stencil_pipe.h); stencilk_rects_gpu routes
 //     kernels 9/10 here. stages = waves per strip (0: pipe_default_stages).
 //     pipe is bitwise equal to kernel 5 and to stencilk5_rects_cpu; pipec to K
 //     one-step launches and stencilk_rects_cpu.
+//   12 piper / 22 piper_nosb: pipe with register-resident factors (K = 10..24
+//     / K = 20, 24), bitwise equal to pipe. Kernel = 9 + arithmetic id
+//     (pipe_arith.h); 11 and 13-21, 23-29 are retired (docs/TUNING.md).
 constexpr int kPipeMaxK = 24;
 int pipe_default_stages(int K);
 bool pipe_has(int K, int stages, int arith = 0);
@@ -129,7 +131,7 @@ int pipe_vec(int K, int stages, int arith, int64_t nx, int requested, bool align
 // (K, stages, arith, V): the
 // executor prices direct-store passes with it (DiffusionExecutor::set_direct).
 void stencil_pipe_occupancy(int K, int stages, int arith, int V, int occ[2]);
-// arith: 0 fast5, 1 canonical, 2 fast5 with ds_bpermute lane moves (kernel 11)
+// arith: the ids of pipe_arith.h (0 fast5, 1 canonical, 3 / 13 register factors)
 void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const double* T,
                             const double* iCp, int64_t nx, int64_t ny, const Rect* rects,
                             int nrects, const StencilCoef& c, const StencilTuning& tune,
@@ -140,11 +142,6 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
 void stencil5_rects_cpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
                         const Rect* rects, int nrects, const StencilCoef& c);
 void stencilk5_rects_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
-                         int64_t ny, const Rect* rects, int nrects, const StencilCoef& c);
-// the split fast-math form (kernels 14 / 15), see stencil_pipe.h kArFast6Reg
-void stencil6_rects_cpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
-                        const Rect* rects, int nrects, const StencilCoef& c);
-void stencilk6_rects_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
                          int64_t ny, const Rect* rects, int nrects, const StencilCoef& c);
 
 // Width (in cells) of one wave's x-strip in the march kernel; perf_hide rounds

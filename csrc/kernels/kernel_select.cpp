@@ -26,22 +26,9 @@ int pipe_default_stages(int K) {
 
 bool pipe_has(int K, int S, int arith) {
   if (K < 1 || K > kPipeMaxK) return false;
-  if (arith == pipe::kArFast5Perm) return S == 4 && (K == 16 || K == 20 || K == 24);
   if (arith == pipe::kArFast5Reg) return S == 4 && K >= 10 && K <= 24;
-  if (arith == pipe::kArDiagOneRow) return S == 4 && (K == 20 || K == 24);
-  if (pipe::ar_split(arith)) return S == 4 && (K == 20 || K == 24);
-  if (arith == pipe::kArFast5RegU3) return S == 4 && K >= 17 && K <= 20;
-  if (arith == pipe::kArFast5RegIso) return S == 4 && (K == 20 || K == 24);
-  if (arith == pipe::kArDiagS0) return S == 4 && K == 20;
-  if (arith == pipe::kArFast5RegW1) return S == 4 && (K == 20 || K == 24);
-  if (arith == pipe::kArFast5RegMask || arith == pipe::kArFast5RegMaskCtl ||
-      arith == pipe::kArFast5RegNoSB || arith == pipe::kArFast5RegRot)
-    return S == 4 && (K == 20 || K == 24);
-  if (arith == pipe::kArDiagHalfBarrier) return S == 4 && K == 20;
-  if (arith == pipe::kArFast5RegU6S) return S == 4 && (K == 21 || K == 24);
-  if (arith == pipe::kArFast5RegSP || arith == pipe::kArFast5RegSP2 ||
-      arith == pipe::kArFast5RegPrio || arith == pipe::kArFast5RegPrioNR)
-    return S == 4 && (K == 20 || K == 24);
+  if (arith == pipe::kArFast5RegNoSB) return S == 4 && (K == 20 || K == 24);
+  if (arith != pipe::kArFast5 && arith != pipe::kArCanon) return false;  // retired ids
   if (S == pipe_default_stages(K)) return true;
   // alternative stage splits instantiated for sweeps (csrc/lab/stencil_pipe_lab.hip)
   return (K == 12 && S == 3) || (K == 16 && S == 8) || (K == 24 && S == 8) ||
@@ -51,15 +38,14 @@ bool pipe_has(int K, int S, int arith) {
 bool pipe_has_cols(int K, int S, int arith, int cols) {
   if (cols <= 1) return pipe_has(K, S, arith);
   if (cols != 2 || S != 4) return false;
-  if (arith == pipe::kArFast5 || arith == pipe::kArFast5Reg) return K == 16 || K == 20 || K == 24;
-  return arith == pipe::kArFast5RegRot && (K == 20 || K == 24);
+  return (arith == pipe::kArFast5 || arith == pipe::kArFast5Reg) && (K == 16 || K == 20 || K == 24);
 }
 
 int pipe_default_cols(int K, int S, int arith) {
   // one column wave: the 2-column blocks (csrc/lab/stencil_pipe_lab.hip) do 6-8 % less
   // arithmetic but run one 8-wave block per CU and lose more to the unhidden
   // per-row barrier: ring kernel 5-20 % (profiles/pass_sweep_cols2_r2.json), piper
-  // +5.3 % at K=20 and +11.9 % at K=24 with the rotated map, +34-38 % wait cycles
+  // +5.3 % at K=20 and +11.9 % at K=24 even with the retired rotated map, +34-38 % wait cycles
   // (profiles/r6/cols2_piper.md)
   (void)K;
   (void)S;

@@ -17,16 +17,17 @@
 // ONE 20-step pass (~70 ms) instead of 16 + 4 (each pass costs at least one
 // HBM sweep of the 3 arrays, ~40 ms at the 288 GB tile).
 //
-// Arithmetic (template Ar: kArFast5 = 0, kArCanon = 1; kArFast5Perm = 2 is
-// fast5 with the lane moves done by ds_bpermute on the LDS pipe instead of
-// DPP on the VALU, an energy / issue experiment, profiles/SUMMARY_r2.md):
-//   false  fast5: T2 = fma(g, fma(r, U+D, fma(-2(1+r), c, L+R)), c), g = dt*lam/dx^2/Cp
+// Arithmetic (template Ar, the ids of pipe_arith.h):
+//   kArFast5   T2 = fma(g, fma(r, U+D, fma(-2(1+r), c, L+R)), c), g = dt*lam/dx^2/Cp
 //          (LDS ring holds g, zero outside the interior). Bitwise equal to
 //          kernel 5 (csrc/lab) and to the CPU twin stencilk5_rects_cpu.
-//   true   the canonical flux form of rma/common.h (scripts/diffusion_2D_perf.jl:8-10
+//   kArCanon   the canonical flux form of rma/common.h (scripts/diffusion_2D_perf.jl:8-10
 //          with 1/Cp): x face flux shared with the left lane, y face flux
 //          carried from the previous row; bitwise equal to K one-step launches.
 //          The ring holds 1/Cp (zero outside the interior: c + dt*(0*...) == c).
+//   kArFast5Reg, kArFast5RegNoSB   fast5 with the factor rows in registers
+//          instead of the ring (below, "Register-resident factors"); NoSB
+//          without the sched_barriers inside a level. Bitwise equal to kArFast5.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -96,7 +97,7 @@ struct Geo {
 // 3 rows x V cells x 2 dwords per level, stage 0's two-row prefetch, ~40 for
 // addressing and temporaries; canonical also the carried y flux and the x
 // fluxes (checked: no spills at any K, V, scripts/check_isa.py).
-// arithmetic template ids (kAr*), ar_reg / ar_split: pipe_arith.h (host-safe)
+// arithmetic template ids (kAr*), ar_reg: pipe_arith.h (host-safe)
 
 template <int K, int S, int V, bool Canon, int C = 1>
 constexpr int occupancy(int lds) {
@@ -137,21 +138,15 @@ constexpr int waves_per_simd() {
   return occupancy<K, S, V, Canon, C>(lds_bytes<K, S, V, Canon, C>());
 }
 
-// Register-resident factors (Ar = kArFast5Reg, "piper"): no factor ring. A
+// Register-resident factors (ar_reg(Ar), "piper"): no factor ring. A
 // stage keeps the factor rows of its H levels in registers (a shift register:
 // level j+1 uses next row iteration the row level j uses now), and each stage
 // hands the row it retires to the next stage through a double-buffered LDS
 // row, like the T hand-off. LDS read bytes per cell update: the ring's one
 // factor row per level -> one factor row per stage (H levels); LDS per
 // block: 4 (S-1) rows.
-#ifndef RMA_PIPE_U6
-#define RMA_PIPE_U6 1
-#endif
-constexpr bool kPipeU6 = RMA_PIPE_U6;
-#ifndef RMA_PIPE_U6_H6  // experiments only: unroll by 6 also at H = 6 (spills, see below)
-#define RMA_PIPE_U6_H6 0
-#endif
-// Register factors: a factor row lives H iterations and a new one starts
+//
+// The row loop (pipe_u6): a factor row lives H iterations and a new one starts
 // every iteration, so with the row loop unrolled by U < H the row started at
 // phase p is still live when the next trip's phase-p row starts and the back
 // edge has to move every row (20 v_mov_b64 per 3 rows at K=20: ~5 % of the
@@ -162,10 +157,7 @@ constexpr bool kPipeU6 = RMA_PIPE_U6;
 // K=20: 247 instead of 201 VGPRs, no spill, still 2 waves per SIMD.
 template <int K, int S, int Ar>
 constexpr bool pipe_u6() {
-  return ar_reg(Ar) && kPipeU6 && Ar != kArFast5RegU3 &&
-         (Plan<K, S>::H == 5 ||
-          ((Ar == kArFast5RegW1 || Ar == kArFast5RegU6S || (RMA_PIPE_U6_H6 && Ar == kArFast5Reg)) &&
-           Plan<K, S>::H == 6));
+  return ar_reg(Ar) && Plan<K, S>::H == 5;
 }
 // LDS-DMA staging rows per array: one per phase of the unrolled row loop, so
 // a row DMA'd at phase p is read at phase p of the next loop trip (across the
@@ -192,34 +184,24 @@ constexpr int kernel_waves() {
     constexpr int vgpr = 8 * H * V + 8 * V + 40;
     constexpr int by_vgpr = 512 / ((vgpr + 7) / 8 * 8);
     constexpr int w = occupancy<K, S, V, false, C>(lds_bytes_reg<K, S, V, Ar, C>());
-    if constexpr (Ar == kArFast5RegW1) return 1;
     return by_vgpr < 2 ? 2 : (by_vgpr < w ? by_vgpr : w);
   } else {
     return waves_per_simd<K, S, V, Ar == kArCanon, C>();
   }
 }
 
-template <bool kDpp = true>
+// lane moves by DPP on the VALU
 __device__ __forceinline__ double from_next_lane(double v) {
-  if constexpr (kDpp) {
-    // wave_shl:1 (lane i <- lane i+1); bound_ctrl: lane 63 reads 0 (invalid column)
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x130, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-  } else {
-    return __shfl_down(v, 1);  // ds_bpermute x2 (LDS pipe); lane 63: its own value
-  }
+  // wave_shl:1 (lane i <- lane i+1); bound_ctrl: lane 63 reads 0 (invalid column)
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x130, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
 }
-template <bool kDpp = true>
 __device__ __forceinline__ double from_prev_lane(double v) {
-  if constexpr (kDpp) {
-    // wave_shr:1 (lane i <- lane i-1); lane 0 reads 0 (invalid column)
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x138, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-  } else {
-    return __shfl_up(v, 1);  // lane 0: its own value (an invalid column either way)
-  }
+  // wave_shr:1 (lane i <- lane i-1); lane 0 reads 0 (invalid column)
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x138, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x138, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
 }
 
 // Direct-store halos of one stored row (DirectStores, kernels.h): the row's
@@ -258,7 +240,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
                                           const RectList& L, const StencilCoef& k, int chunk_rows,
                                           int remap, const DirectStores& DS) {
   using P = Plan<K, S>;
-  constexpr bool Canon = Ar == kArCanon, kDpp = Ar != kArFast5Perm, kRegG = ar_reg(Ar);
+  constexpr bool Canon = Ar == kArCanon, kRegG = ar_reg(Ar);
   static_assert(!kRegG || (V != 5 && (C == 1 || V == 4)),
                 "register factors: V <= 4; two column waves at V = 4 only");
   // register factors, 2 or 4 cells per lane: stage 0 prefetches T / 1/Cp three
@@ -282,16 +264,9 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   constexpr int NH = S > 1 ? S - 1 : 1;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col = C > 1 ? wv / S : 0;
-  // waves c*S .. c*S+S-1: column c, one per SIMD (waves are dealt to SIMDs in
-  // order). Rotated maps: odd blocks (C = 1) / column 1 (C = 2) start at SIMD
-  // 2, so no SIMD hosts two stage-0 waves
-  const int stage = (Ar == kArFast5RegRot || Ar == kArFast5RegPrio)
-                        ? (C > 1 ? (wv % S + 2 * col) % S : (wv + 2 * (int)(blockIdx.x & 1)) % S)
-                        : wv % S;
+  // waves c*S .. c*S+S-1: column c, one per SIMD (waves are dealt to SIMDs in order)
+  const int stage = wv % S;
   const int lane = threadIdx.x & (kWave - 1);
-  if constexpr (Ar == kArFast5RegPrio || Ar == kArFast5RegPrioNR) {
-    if (stage == 0) __builtin_amdgcn_s_setprio(2);  // wave-uniform
-  }
   const int64_t sig_first = L.sig ? L.sig_blocks : 0;
   const int64_t b = remap ? xcd_remap_after(blockIdx.x, gridDim.x, sig_first) : (int64_t)blockIdx.x;
   int ri = 0;
@@ -483,22 +458,13 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   for (int v = 0; v < V; ++v) gp[v] = 0.0;
   int par = 0;
   const int lag = stage * (H + 1);  // rows behind stage 0
-  // kArFast5RegMask: per local level, is any of this lane's cells inside the
-  // level's valid cone (loop-invariant lane masks, kept in SGPR pairs)
-  constexpr bool kMask = (Ar == kArFast5RegMask || Ar == kArFast5RegMaskCtl) && V == 4;  // other V: plain piper
-  uint64_t amask[kMask ? H : 1];
-#pragma unroll
-  for (int j = 1; j <= (kMask ? H : 1); ++j) {
-    const int l = stage * H + j;
-    amask[j - 1] = __ballot(Ar == kArFast5RegMaskCtl || (lane * V + V > l && lane * V < W - l));
-  }
 
   auto iter = [&](auto Pc, auto S0c, auto LASTc) {
     constexpr int Ps = decltype(Pc)::value;  // phase of the unrolled loop (staging slot)
     constexpr int Pr = Ps % 3;                // phase of the 3-row windows w
     constexpr bool S0 = decltype(S0c)::value;
     constexpr bool LAST = decltype(LASTc)::value;
-    constexpr int NL = LAST ? HL : (S0 && Ar == kArDiagS0 ? H - 1 : H);  // levels of this stage
+    constexpr int NL = LAST ? HL : H;  // levels of this stage
     constexpr int PC = (Pr + 2) % 3, PU = (Pr + 1) % 3;
     double g[V];
     if constexpr (S0) {
@@ -604,8 +570,6 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
     } else {
       rd2(ring_row(1), gn);
     }
-    constexpr bool kSP = Ar == kArFast5RegSP || Ar == kArFast5RegSP2;
-    double tq[kSP ? V : 1];  // software pipelining: the next level's fma(mkc, c, L+R)
 #pragma unroll
     for (int j = 1; j <= NL; ++j) {
       const int row = i - (S0 ? 0 : lag) - (j - 1);
@@ -616,85 +580,15 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
       } else {
 #pragma unroll
         for (int v = 0; v < V; ++v) gl[v] = gn[v];
-        if (j < NL && Ar != kArDiagOneRow) fetch(j + 1, gn);
+        if (j < NL) fetch(j + 1, gn);
       }
       const double(&c)[V] = w[j - 1][PC];
       const double(&dn)[V] = w[j - 1][Pr];
       double res[V];
-      uint64_t saved_exec = 0;
       if constexpr (!Canon) {
         const double(&up)[V] = w[j - 1][PU];
-        const double rn = from_next_lane<kDpp>(c[0]);
-        const double ln = from_prev_lane<kDpp>(c[V - 1]);
-        if constexpr (kMask) {
-          // the level's arithmetic in ONE asm statement under the cone's lane
-          // mask (the compiler can place nothing of its own under the narrowed
-          // EXEC); the lane moves above ran under the full EXEC (a neighbour
-          // may skip the level). Same operations and order as below, per cell:
-          // sx = L + R; t = fma(mkc, c, sx); t = fma(ry, U + D, t);
-          // res = fma(g, t, c). Inactive lanes keep stale registers that no
-          // valid output reads. s_nop 1: VALU write -> DPP read wait states.
-          // In place where the input dies here: L + R of cell 0 / 3 into the lane
-          // moves' registers, U + D into the oldest row `up` (dead after this level).
-          double(&um)[V] = w[j - 1][PU];
-          res[0] = ln;
-          res[3] = rn;
-          asm volatile(
-              "s_and_saveexec_b64 %[sv], %[m]\n\t"
-              "v_add_f64 %[r0], %[c1], %[r0]\n\t"
-              "v_add_f64 %[r1], %[c2], %[c0]\n\t"
-              "v_add_f64 %[r2], %[c3], %[c1]\n\t"
-              "v_add_f64 %[r3], %[r3], %[c2]\n\t"
-              "v_add_f64 %[u0], %[u0], %[d0]\n\t"
-              "v_add_f64 %[u1], %[u1], %[d1]\n\t"
-              "v_add_f64 %[u2], %[u2], %[d2]\n\t"
-              "v_add_f64 %[u3], %[u3], %[d3]\n\t"
-              "v_fma_f64 %[r0], %[mk], %[c0], %[r0]\n\t"
-              "v_fma_f64 %[r1], %[mk], %[c1], %[r1]\n\t"
-              "v_fma_f64 %[r2], %[mk], %[c2], %[r2]\n\t"
-              "v_fma_f64 %[r3], %[mk], %[c3], %[r3]\n\t"
-              "v_fma_f64 %[r0], %[ry], %[u0], %[r0]\n\t"
-              "v_fma_f64 %[r1], %[ry], %[u1], %[r1]\n\t"
-              "v_fma_f64 %[r2], %[ry], %[u2], %[r2]\n\t"
-              "v_fma_f64 %[r3], %[ry], %[u3], %[r3]\n\t"
-              "v_fma_f64 %[r0], %[g0], %[r0], %[c0]\n\t"
-              "v_fma_f64 %[r1], %[g1], %[r1], %[c1]\n\t"
-              "v_fma_f64 %[r2], %[g2], %[r2], %[c2]\n\t"
-              "v_fma_f64 %[r3], %[g3], %[r3], %[c3]\n\t"
-              "s_or_b64 exec, exec, %[sv]\n\t"
-              "s_nop 1"
-              : [r0] "+v"(res[0]), [r1] "=&v"(res[1]), [r2] "=&v"(res[2]), [r3] "+v"(res[3]),
-                [u0] "+v"(um[0]), [u1] "+v"(um[1]), [u2] "+v"(um[2]), [u3] "+v"(um[3]),
-                [sv] "=&s"(saved_exec)
-              : [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]),
-                [d0] "v"(dn[0]), [d1] "v"(dn[1]), [d2] "v"(dn[2]), [d3] "v"(dn[3]),
-                [g0] "v"(gl[0]), [g1] "v"(gl[1]), [g2] "v"(gl[2]), [g3] "v"(gl[3]),
-                [ry] "v"(ry), [mk] "v"(mkc), [m] "s"(amask[j - 1])
-              : "scc");
-        } else if constexpr (kSP) {
-          auto partial = [&](const double(&cc)[V], double r_n, double l_n, double(&out)[V]) {
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-              const double rv = v + 1 < V ? cc[v + 1] : r_n;
-              const double lv = v > 0 ? cc[v - 1] : l_n;
-              out[v] = __builtin_fma(mkc, cc[v], rv + lv);
-            }
-          };
-          if (j == 1) partial(c, rn, ln, tq);
-          double t[V];
-#pragma unroll
-          for (int v = 0; v < V; ++v) t[v] = tq[v];
-          if (j < NL) {  // the next level's centre row: the previous row iteration's
-            const double(&cn)[V] = w[j][PC];
-            partial(cn, from_next_lane<kDpp>(cn[0]), from_prev_lane<kDpp>(cn[V - 1]), tq);
-          }
-#pragma unroll
-          for (int v = 0; v < V; ++v) {
-            t[v] = __builtin_fma(ry, up[v] + dn[v], t[v]);
-            res[v] = __builtin_fma(gl[v], t[v], c[v]);
-          }
-          if constexpr (Ar == kArFast5RegSP) __builtin_amdgcn_sched_barrier(0);
-        } else {
+        const double rn = from_next_lane(c[0]);
+        const double ln = from_prev_lane(c[V - 1]);
         double sx[V], sy[V], t[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -705,41 +599,14 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
         }
         // the V cells' FMA chains interleaved (sched_barrier keeps them apart)
         if constexpr (Ar != kArFast5RegNoSB) __builtin_amdgcn_sched_barrier(0);
-        if constexpr (ar_split(Ar)) {
-          double u[V];
-          if constexpr (Ar == kArFast6Reg) {
 #pragma unroll
-            for (int v = 0; v < V; ++v) {
-              u[v] = __builtin_fma(-2.0, c[v], sx[v]);
-              t[v] = __builtin_fma(-2.0, c[v], sy[v]);
-            }
-          } else {
+        for (int v = 0; v < V; ++v) t[v] = __builtin_fma(mkc, c[v], sx[v]);
+        if constexpr (Ar != kArFast5RegNoSB) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int v = 0; v < V; ++v) {
-              const double d = c[v] + c[v];
-              u[v] = sx[v] - d;
-              t[v] = sy[v] - d;
-            }
-          }
-          if constexpr (Ar != kArFast5RegNoSB) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int v = 0; v < V; ++v) t[v] = __builtin_fma(ry, t[v], u[v]);
-        } else {
-#pragma unroll
-          for (int v = 0; v < V; ++v) t[v] = __builtin_fma(mkc, c[v], sx[v]);
-          if constexpr (Ar != kArFast5RegNoSB) __builtin_amdgcn_sched_barrier(0);
-          if constexpr (Ar == kArFast5RegIso) {
-#pragma unroll
-            for (int v = 0; v < V; ++v) t[v] = sy[v] + t[v];
-          } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v) t[v] = __builtin_fma(ry, sy[v], t[v]);
-          }
-        }
+        for (int v = 0; v < V; ++v) t[v] = __builtin_fma(ry, sy[v], t[v]);
         if constexpr (Ar != kArFast5RegNoSB) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int v = 0; v < V; ++v) res[v] = __builtin_fma(gl[v], t[v], c[v]);
-        }  // !kMask
       } else {
         // canonical: same expressions and rounding as rma/common.h
         const double rn = from_next_lane(c[0]);
@@ -759,7 +626,6 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
           res[v] = c[v] + k.dt * (gl[v] * ((-(qr[v] - qL)) * k.rdx - (qU - qD) * k.rdy));
         }
       }
-      (void)saved_exec;
       if (j < NL) {
         const int jj = j < NL ? j : NL - 1;
 #pragma unroll
@@ -801,10 +667,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
         glds_row(0, i + 1 + NST, Ps);
         glds_row(1, i + NST, Ps);
       }
-      if (Ar != kArDiagHalfBarrier || (Ps & 1))
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     } else {
       __syncthreads();  // hand-off and ring rows visible; this iteration's reads done
     }
@@ -939,8 +802,8 @@ void launch(const PipeLaunch& a) {
 
 // Each stencil_pipe_{a,b,c}.hip unit instantiates a range of (K, S) of the
 // default stage split and answers for it: returns false if it does not hold
-// (K, S, V, arithmetic). Alternative splits, the ds_bpermute variant and the
-// two-column blocks are in the lab library (csrc/lab/stencil_pipe_lab.hip).
+// (K, S, V, arithmetic). Alternative splits, the two-column blocks and 5 cells
+// per lane are in the lab library (csrc/lab/stencil_pipe_lab.hip).
 bool dispatch_a(int K, int S, int V, int ar, const PipeLaunch& a);
 bool dispatch_b(int K, int S, int V, int ar, const PipeLaunch& a);
 bool dispatch_c(int K, int S, int V, int ar, const PipeLaunch& a);

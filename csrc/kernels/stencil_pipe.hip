@@ -1,7 +1,8 @@
 // Host side of the any-K stage-pipelined kernel (stencil_pipe.h): argument
 // checks, strip/chunk planning and the (K, S, V, arithmetic) dispatch over the
-// instantiation units stencil_pipe_{a,b,c}.hip (default stage split); any
-// other (K, S, V, C, arithmetic) goes to the lab library (lab_hooks.h).
+// instantiation units stencil_pipe_{a,b,c,r,r20,r24}.hip (default stage split,
+// one column wave); any other (K, S, V, C, arithmetic) that pipe_has /
+// pipe_has_cols admit goes to the lab library (lab_hooks.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,11 +42,6 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
                 "pipelined K-step kernel: 1 <= K <= " << kPipeMaxK << ", got " << K);
   RMA_CHECK_ARG(pipe_has(K, S, arith), "no pipelined kernel instantiated for K=" << K << " S=" << S
                                                                              << " arithmetic " << arith);
-  RMA_CHECK_ARG(arith >= 0 && arith <= 20, "pipelined kernel arithmetic " << arith);
-  if (arith == pipe::kArFast5RegIso) {
-    const double ax = (-c.mlam) * c.rdx * c.rdx, ay = (-c.mlam) * c.rdy * c.rdy;
-    RMA_CHECK_ARG(ay / ax == 1.0, "the isotropic fast-math kernel needs ry = (dx/dy)^2 == 1");
-  }
   const bool canonical = arith == pipe::kArCanon;
   RMA_CHECK_ARG(canonical || fast5_ok(c),
                 "the fast5 arithmetic folds dy^-2/dx^-2 into one factor: needs lam != 0 and "
@@ -106,7 +102,7 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
            pipe::dispatch_r(K, S, V, arith, a) ||
              pipe::dispatch_a(K, S, V, arith, a) ||
              pipe::dispatch_b(K, S, V, arith, a) || pipe::dispatch_c(K, S, V, arith, a));
-  if (!ok) {  // alternative stage splits, pipeb, two-column blocks, 5 cells: librma_lab.so
+  if (!ok) {  // alternative stage splits, two-column blocks, 5 cells: librma_lab.so
     if (!lab_hooks().pipe)
       lab_missing("this pipelined kernel variant (stages / arithmetic / cols / 5 cells per lane)");
     ok = lab_hooks().pipe(K, S, V, C, arith, a);

@@ -39,42 +39,17 @@ Rect = tuple  # (x0, x1, y0, y1), half-open, 0-based cell indices
 # test oracles and for sweeps), loaded on first use: K-step "march"/"lds"/"dpp" (0/1/2:
 # canonical variants of kernel 3), "fast" (4: reassociated, not bitwise), "fast5" (5: the
 # 5-point sum with one folded per-cell factor, the GPU oracle of "pipe"), "fast5p2/p4/p8"
-# (6/7/8: fixed-K pipelined fast5), "pipeb" (11: pipe with ds_bpermute lane moves), and
-# the pipelined kernels' non-default stage splits, two-column blocks and 5 cells per lane,
-# "pipe_diag1" (13: a diagnosis, WRONG results: one factor-ring read per stage and row),
-# and "piper6" / "piper7" (14 / 15: register factors with the split fast-math form for
-# dx != dy, T2 = fma(g, fma(ry, fma(-2,c,U+D), fma(-2,c,L+R)), c); CPU twin: FAST6), and
-# "piper_u3" (16: piper with the round-3 unroll by 3, an A/B of the core's unroll by 6),
-# "piper_iso" (17: piper for ry == 1 exactly, the y-sum FMA by 1 as an add; bitwise = piper),
-# "piper_diag_s0" (18: a diagnosis, WRONG results: stage 0 runs one level fewer),
-# "piper_w1" (19: piper at one wave per SIMD, unrolled by 6 also at K = 21..24),
-# "piper_mask" (20: piper whose lanes outside a level's valid cone skip it; bitwise = piper)
-# and its control "piper_mask_ctl" (21: the same asm arithmetic under the full EXEC),
-# "piper_nosb" (22: piper without the sched_barriers inside a level; bitwise = piper),
-# "piper_rot" (23: piper with the stage -> wave map rotated by 2 in odd blocks),
-# "piper_diag_hb" (24: a diagnosis, WRONG results: the row barrier every other row only),
-# "piper_u6s" (25: piper unrolled by 6 also at K = 21..24, spilling),
-# "piper_sp" / "piper_sp2" (26 / 27: levels software-pipelined, with / without a
-# sched_barrier per level; bitwise = piper), "piper_prio" (28: the rotated stage map
-# plus s_setprio for stage-0 waves) and its control "piper_prio_nr" (29: the
-# priority without the rotation); bitwise = piper.
-FAST5 = ("fast5", "fast5p2", "fast5p4", "fast5p8", "pipe", "pipeb", "piper", "piper_u3",
-         "piper_iso", "piper_diag_s0", "piper_w1", "piper_mask", "piper_mask_ctl", "piper_nosb",
-         "piper_rot", "piper_diag_hb", "piper_u6s",
-         "piper_sp", "piper_sp2", "piper_prio", "piper_prio_nr")
-FAST6 = ("piper6", "piper7")
-PIPE = ("pipe", "pipec", "pipeb", "piper", "pipe_diag1", "piper6", "piper7", "piper_u3",
-        "piper_iso", "piper_diag_s0", "piper_w1", "piper_mask", "piper_mask_ctl", "piper_nosb",
-         "piper_rot", "piper_diag_hb", "piper_u6s",
-         "piper_sp", "piper_sp2", "piper_prio", "piper_prio_nr")
+# (6/7/8: fixed-K pipelined fast5), the pipelined kernels' non-default stage splits,
+# two-column blocks and 5 cells per lane, and "piper_nosb" (22: piper without the
+# sched_barriers inside a level; bitwise = piper) at K = 20; its K = 24 is the executor's
+# kernel and in the core. Kernel ids 11, 13-21 and 23-29 are retired experiments
+# (docs/TUNING.md, "Retired kernel experiments").
+FAST5 = ("fast5", "fast5p2", "fast5p4", "fast5p8", "pipe", "piper", "piper_nosb")
+PIPE = ("pipe", "pipec", "piper", "piper_nosb")
 PIPE_MAX_K = 24
 KERNELS = {"march": 0, "lds_dpp": 3, "pipe": 9, "pipec": 10, "piper": 12}
 LAB_KERNELS = {"lds": 1, "dpp": 2, "fast": 4, "fast5": 5, "fast5p2": 6, "fast5p4": 7, "fast5p8": 8,
-               "pipeb": 11, "pipe_diag1": 13, "piper6": 14, "piper7": 15,
-               "piper_u3": 16, "piper_iso": 17, "piper_diag_s0": 18, "piper_w1": 19,
-               "piper_mask": 20, "piper_mask_ctl": 21, "piper_nosb": 22, "piper_rot": 23,
-               "piper_diag_hb": 24, "piper_u6s": 25, "piper_sp": 26, "piper_sp2": 27,
-               "piper_prio": 28, "piper_prio_nr": 29}
+               "piper_nosb": 22}
 KSTEP_CORE = ("lds_dpp", "pipe", "pipec", "piper")
 
 
@@ -317,7 +292,7 @@ def stencilk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor,
         ch = native().default_chunk_k(K, ny) if has_native() else 16
         tuning = StencilTuning(chunk_rows=ch, kernel="lds_dpp", xcd_remap=1)
     tn = tuning
-    if tn.kernel in FAST5 + FAST6 and not fast5_ok(coef):
+    if tn.kernel in FAST5 and not fast5_ok(coef):
         raise ValueError("kernel 'fast5' folds dy^-2/dx^-2 into one factor: needs lam != 0 "
                          f"and finite coefficients, got {tuple(coef)}")
     if T.is_cuda:

@@ -42,15 +42,15 @@ for s in "$@"; do
     sweep5) step sweep5 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe 16,20,24 \
              --pipe5 16-20 --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweep5.json" || exit 1 ;;
     sweep5b) step sweep5b 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe 20,24 \
-             --pipe5 20 --chunks5 20:1536/2048/4096 --kinds piper:20,piper:24,pipe_diag1:20,pipe_diag1:24 \
+             --pipe5 20 --chunks5 20:1536/2048/4096 --kinds piper:20,piper:24 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweep5b.json" || exit 1 ;;
     pmc5a) prof pmc5a 300 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS \
              SQ_ACTIVE_INST_SCA SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CU_CYCLES SQ_INSTS_LDS GRBM_GUI_ACTIVE \
              --output-format csv -d "$R/$OUT/pmc5a" -o run -- python3 "$R/bench/pass_sweep.py" \
-             --n 101120 --rounds 2 --pipe 20,24 --pipe5 20 --kinds pipe_diag1:24 --pipec "" \
+             --n 101120 --rounds 2 --pipe 20,24 --pipe5 20 --pipec "" \
              --ldsdpp "" --old "" --alt "" || exit 1 ;;
     sweepr) step sweepr 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe 12,16,20,24 \
-             --pipe5 20 --kinds piper:12,piper:16,piper:20,piper:24,pipe_diag1:24 \
+             --pipe5 20 --kinds piper:12,piper:16,piper:20,piper:24 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepr.json" || exit 1 ;;
     sweepr2) step sweepr2 600 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe 16,20,24 \
              --pipe5 20 --kinds piper:20,piper:24 \
@@ -64,12 +64,12 @@ for s in "$@"; do
              --kinds piper:17,piper:18,piper:19,piper:20 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepr3.json" || exit 1 ;;
     sweepg) step sweepg 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe 20,21,22,23,24 \
-             --kinds piper:20,piper:21,piper:22,piper:23,piper:24,pipe_diag1:24 \
+             --kinds piper:20,piper:21,piper:22,piper:23,piper:24 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepg.json" || exit 1 ;;
     pmcg) prof pmcg 300 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS \
              SQ_ACTIVE_INST_SCA SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CU_CYCLES SQ_INSTS_LDS GRBM_GUI_ACTIVE \
              --output-format csv -d "$R/$OUT/pmcg" -o run -- python3 "$R/bench/pass_sweep.py" \
-             --n 101120 --rounds 1 --pipe 20,24 --kinds piper:20,piper:24,pipe_diag1:24 --pipec "" \
+             --n 101120 --rounds 1 --pipe 20,24 --kinds piper:20,piper:24 --pipec "" \
              --ldsdpp "" --old "" --alt "" || exit 1 ;;
     sweepg_small) step sweepg_small 600 python bench/pass_sweep.py --n 16384 --rounds 7 \
              --pipe 17,20,24 --kinds piper:17,piper:20,piper:24 --pipec "" --ldsdpp "" --old "" \
@@ -113,16 +113,8 @@ for s in "$@"; do
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/sweepc2.json" || exit 1 ;;
     coef_ab) step coef_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
              --pipec "" --ldsdpp "" --old "" --alt "" --coef-dims 4,2 --coef-alt 1,1 \
-             --kinds piper:20,piper:24,piper6:20,piper6:24,piper7:20,piper7:24 \
+             --kinds piper:20,piper:24 \
              --out "$OUT/coef_ab.json" || exit 1 ;;
-    u6_ab) step u6_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:17,piper:18,piper:19,piper:20,piper_u3:17,piper_u3:18,piper_u3:19,piper_u3:20 \
-             --out "$OUT/u6_ab.json" || exit 1 ;;
-    iso_ab) step iso_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" --coef-dims 1,1 \
-             --kinds piper:20,piper:24,piper_iso:20,piper_iso:24,piper_u3:20 \
-             --out "$OUT/iso_ab.json" || exit 1 ;;
     eqsmall) for t in eqn4096_x eqn4096_x_cd2 eqn4096_xy eqn4096_xy_cd2 eqn4096_xy_strips \
                       eqn8192_xy eqn8192_xy_cd2; do bash "$0" OUT="$OUT" "$t" || exit 1; done ;;
     eqsmall2) for t in eqn4096_xy_cd2_bol eqn4096_xy_bol eqn4096_xy_cd4_bol eqn4096_x_cd4 \
@@ -137,17 +129,9 @@ for s in "$@"; do
     chunk20) step chunk20 600 python bench/pass_sweep.py --n 101120 --rounds 5 --pipe "" \
              --kinds piper:20:2560,piper:20:2816,piper:20:2890,piper:20:2976,piper:20,piper:20:3160,piper:20:3328 \
              --pipec "" --ldsdpp "" --old "" --alt "" --out "$OUT/chunk20.json" || exit 1 ;;
-    u6_small) for n in 16384 8192 4096; do
-               step u6_$n 600 python bench/pass_sweep.py --n $n --rounds 9 --pipe "" --pipec "" \
-               --ldsdpp "" --old "" --alt "" \
-               --kinds piper:17,piper:18,piper:19,piper:20,piper_u3:17,piper_u3:18,piper_u3:19,piper_u3:20 \
-               --out "$OUT/u6_$n.json" || exit 1; done ;;
     exec_costs) for n in 101120 16384 8192 4096; do
                step exec_$n 600 python bench/pass_sweep.py --n $n --rounds 7 --pipe "" --pipec "" \
                --ldsdpp "" --old "" --alt "" --exec 1-24 --out "$OUT/exec_$n.json" || exit 1; done ;;
-    diag_s0) step diag_s0 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" --kinds piper:20,piper_diag_s0:20 \
-             --out "$OUT/diag_s0.json" || exit 1 ;;
     trace8192y) prof trace8192y 300 --kernel-trace --output-format csv -d "$R/$OUT/trace8192y" \
              -o run -- python3 "$R/bench/rccl_self_overhead.py" --n 8192 --K 24 --variants perf_hide \
              --periodic y --steps 480 --pattern op --spacing equal --out "$R/$OUT/trace8192y.json" || exit 1 ;;
@@ -169,12 +153,6 @@ for s in "$@"; do
     eqlag) for t in eqn2048_xy eqn2048_xy_nolag eqn4096_xy eqn4096_xy_nolag eqn4096_x eqn4096_x_nolag \
                     eqn8192_xy eqn8192_xy_nolag eqn16384_xy eqn16384_xy_nolag; do
                bash "$0" OUT="$OUT" "$t" || exit 1; done ;;
-    w1_ab) step w1_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_w1:20,piper:24,piper_w1:24 --out "$OUT/w1_ab.json" || exit 1 ;;
-    mask_ab) step mask_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_mask:20,piper_mask_ctl:20,piper:24,piper_mask:24,piper_mask_ctl:24 --out "$OUT/mask_ab.json" || exit 1 ;;
     nosb_ab) step nosb_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
              --pipec "" --ldsdpp "" --old "" --alt "" \
              --kinds piper:20,piper_nosb:20,piper:24,piper_nosb:24 --out "$OUT/nosb_ab.json" || exit 1 ;;
@@ -183,28 +161,6 @@ for s in "$@"; do
              step user_example 120 python examples/diffusion_2D_user.py --nx 8192 --ny 8192 --nt 200 && \
              step user_example_hide 120 python examples/diffusion_2D_user.py --nx 8192 --ny 8192 \
                --nt 200 --hide || exit 1 ;;
-    pmc_u6) prof pmc_u6 240 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS \
-             SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE \
-             --output-format csv -d "$R/$OUT/pmc_u6" -o run -- python3 "$R/bench/pass_sweep.py" \
-             --n 101120 --rounds 1 --pipe "" --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_u3:20,piper:24 || exit 1 ;;
-    rot_ab) step rot_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_rot:20,piper:24,piper_rot:24 --out "$OUT/rot_ab.json" || exit 1 ;;
-    prio_ab) step prio_ab 500 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_rot:20,piper_prio:20,piper_prio_nr:20,piper:24,piper_prio:24 \
-             --out "$OUT/prio_ab.json" || exit 1 ;;
-    hb_ab) step hb_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_diag_hb:20 --out "$OUT/hb_ab.json" || exit 1 ;;
-    u6s_ab) step u6s_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:21,piper_u6s:21,piper:24,piper_u6s:24 --out "$OUT/u6s_ab.json" || exit 1 ;;
-    sp_ab) step sp_ab 400 python bench/pass_sweep.py --n 101120 --rounds 7 --pipe "" \
-             --pipec "" --ldsdpp "" --old "" --alt "" \
-             --kinds piper:20,piper_sp:20,piper_sp2:20,piper:24,piper_sp:24,piper_sp2:24 \
-             --out "$OUT/sp_ab.json" || exit 1 ;;
     tests_ipc) step tests_ipc 400 python -u -m pytest -x -v --timeout 120 --timeout-method thread \
              "tests/test_multirank_gpu.py::test_ipc_transport_processes" \
              "tests/test_multirank_gpu.py::test_ipc_transport_temporal_tiles" \
@@ -324,11 +280,7 @@ for s in "$@"; do
     tests_halo) step tests_halo 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread \
              tests/test_halo_gpu.py -p no:cacheprovider || exit 1 ;;
     tests_mask) step tests_mask 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread \
-             "tests/test_pipe_gpu.py::test_piper_masked_cone_bitwise" \
-             "tests/test_pipe_gpu.py::test_piper_schedule_variants_bitwise" \
-             "tests/test_pipe_gpu.py::test_piper_u6_spilling_bitwise" -p no:cacheprovider || exit 1 ;;
-    tests_w1) step tests_w1 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread \
-             "tests/test_pipe_gpu.py::test_piper_one_wave_per_simd_bitwise" -p no:cacheprovider || exit 1 ;;
+             "tests/test_pipe_gpu.py::test_piper_schedule_variants_bitwise" -p no:cacheprovider || exit 1 ;;
     apps_r4) step app_hide16k 300 python -m rocm_mpi_amd.apps.diffusion_2D_perf_hide --nx 16384 \
                --ny 16384 --nt 1000 --json && \
              step app_perf12k 300 python -m rocm_mpi_amd.apps.diffusion_2D_perf --nt 1000 --json && \
@@ -339,9 +291,7 @@ for s in "$@"; do
              step baseline_presets 600 python bench/baseline_configs.py --max-gpus 1 \
                --out "$OUT/baseline_configs.json" || exit 1 ;;
     tests_r4) step tests_r4 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread \
-             tests/test_capi_gpu.py tests/test_bench_gpu.py "tests/test_pipe_gpu.py::test_piper_split_form_bitwise" \
-             "tests/test_pipe_gpu.py::test_piper_unroll6_equals_unroll3" \
-             "tests/test_pipe_gpu.py::test_piper_iso_bitwise_and_refused_when_anisotropic" \
+             tests/test_capi_gpu.py tests/test_bench_gpu.py \
              "tests/test_pipe_gpu.py::test_piper_register_factors_bitwise" \
              "tests/test_temporal_gpu.py::test_headline_kernels_beyond_2e31_cells" \
              -p no:cacheprovider || exit 1 ;;

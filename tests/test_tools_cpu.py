@@ -115,3 +115,28 @@ def test_fast_kernel_choice_by_depth():
     assert N.pipe_vec(20, 0, 3, 101120, 5, True) == 4      # piper: 4 cells
     assert N.pipe_vec(20, 0, 0, 1026, 4, True) == 2        # nx % 4 != 0
     assert N.pipe_vec(20, 0, 0, 1024, 4, False) == 1       # not 16-B aligned
+
+
+def test_retired_pipe_arithmetics_are_refused():
+    """Only the arithmetic ids 0 (pipe), 1 (pipec), 3 (piper) and 13
+    (piper_nosb) of the pipelined kernel exist (csrc/kernels/pipe_arith.h); the
+    retired experiments (docs/TUNING.md section 6) are unknown by name and
+    refused by id (pipe_has_cols with one column is pipe_has)."""
+    from rocm_mpi_amd import ops
+
+    for name in ("pipeb", "piper_mask", "piper_rot"):
+        with pytest.raises(ValueError, match="unknown kernel"):
+            ops.kernel_id(name)
+    nat = pytest.importorskip("rocm_mpi_amd._native")
+    try:
+        N = nat.native()
+    except Exception as e:  # noqa: BLE001
+        pytest.skip(f"native core not built: {e}")
+    alive = (0, 1, 3, 13)
+    assert [ops.kernel_id(k) - 9 for k in ("pipe", "pipec", "piper", "piper_nosb")] == list(alive)
+    for arith in range(-1, 32):
+        for K in (20, 24):
+            for cols in (1, 2):
+                if arith not in alive:
+                    assert not N.pipe_has_cols(K, 4, arith, cols), (K, arith, cols)
+    assert all(N.pipe_has_cols(24, 4, arith, 1) for arith in alive)
