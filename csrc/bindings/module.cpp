@@ -15,6 +15,7 @@
 #include "rma/comm.h"
 #include "rma/common.h"
 #include "rma/executor.h"
+#include "rma/gather.h"
 #include "rma/halo.h"
 #include "rma/ipc.h"
 #include "rma/kernels.h"
@@ -261,6 +262,40 @@ PYBIND11_MODULE(_C, m) {
       copy2d_batch_cpu(c.data(), (int)c.size(), elem_bytes);
   });
   m.def("copy2d_batch_max", [] { return kCopy2dBatch; });
+  // blocks: [(dst, src, dst_row, dst_plane, src_row, src_plane, nx, ny, nz)] in elements,
+  // any number (launches of <= copy_blocks_max() descriptors of one access path)
+  m.def("copy_blocks", [](const std::vector<std::tuple<uintptr_t, uintptr_t, int64_t, int64_t,
+                                                       int64_t, int64_t, int64_t, int64_t,
+                                                       int64_t>>& blocks,
+                          int elem_bytes, uintptr_t stream, bool gpu) {
+    std::vector<BlockCopy> c;
+    for (const auto& t : blocks)
+      c.push_back({P<void>(std::get<0>(t)), P<const void>(std::get<1>(t)), std::get<2>(t),
+                   std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
+                   std::get<7>(t), std::get<8>(t)});
+    if (gpu)
+      copy_blocks_gpu(c.data(), (int64_t)c.size(), elem_bytes, S(stream));
+    else
+      copy_blocks_cpu(c.data(), (int64_t)c.size(), elem_bytes);
+  });
+  m.def("copy_blocks_max", [] { return kCopyBlocksBatch; });
+  // where every rank's block of the IGG-style gather sits in A_global (rma/gather.h)
+  m.def(
+      "gather_plan",
+      [](const std::array<int, 3>& dims, const std::array<int64_t, 3>& size, int elem_bytes) {
+        const GatherPlan p = plan_gather(dims, size, elem_bytes);
+        py::dict d;
+        d["nprocs"] = p.nprocs;
+        d["size_g"] = p.size_g;
+        d["row_pitch_g"] = p.row_pitch_g;
+        d["plane_pitch_g"] = p.plane_pitch_g;
+        d["block_elems"] = p.block_elems;
+        d["coords"] = p.coords;
+        d["offsets"] = p.offset;
+        d["contiguous_in_global"] = p.contiguous_in_global;
+        return d;
+      },
+      py::arg("dims"), py::arg("size"), py::arg("elem_bytes"));
   // the IPC transport's stream-ordered flag kernels (csrc/kernels/flags.hip)
   m.def(
       "flag_wait",

@@ -49,10 +49,34 @@ int rma_neighbors(const rma_grid* g, int out[6]);
  * fastest; elem_bytes per field. Enqueued on `stream` (asynchronous). */
 int rma_update_halo(rma_grid* g, int nfields, void* const* fields, const int64_t* sizes,
                     const int* elem_bytes, void* stream);
-/* gather!: root receives nprocs*bytes (rank-major) from every rank's buffer. */
+/* The RANK-MAJOR gather (not IGG's layout): root receives nprocs*bytes, rank
+ * r's buffer at byte offset r*bytes. Both buffers must be device memory.
+ * Asynchronous on `stream`. For ImplicitGlobalGrid's gather! use
+ * rma_gather_igg. */
 int rma_gather(rma_grid* g, const void* sendbuf, void* recvbuf, size_t bytes, int root,
                void* stream);
-/* barrier-synchronised timers */
+/* ImplicitGlobalGrid gather!: root assembles every rank's A (size_A = nx,ny,nz,
+ * x fastest) at its Cartesian coordinates into A_global (dims .* size_A).
+ * pitch_A = {row pitch, plane pitch} in elements, NULL = dense. A and A_global
+ * may each be host or device memory; A_global may be NULL off-root. Blocking.
+ *
+ * Collective: every rank calls it with the same size_A, elem_bytes (4 or 8)
+ * and root (equal size_A on all ranks is a precondition, as in IGG). Host or
+ * device is found per pointer (hipPointerGetAttributes; an unknown pointer is
+ * host memory); host data passes through device buffers the grid owns, so
+ * RCCL only ever sees device memory. A strided device A (pitch_A: e.g. the
+ * interior T[2:end-1,2:end-1] of a field) is packed on the device. On return
+ * A_global is complete on root and every rank may reuse A; the wait is bounded
+ * by RMA_COMM_TIMEOUT. Refused before any communication, with the argument
+ * named in rma_last_error: NULL A_global on root, elem_bytes other than 4 / 8,
+ * an extent <= 0, a pitch smaller than the extent, root out of range, and an
+ * A_global of more than RMA_GATHER_MAX_BYTES (default 8 GiB). Only tested
+ * between ranks sharing one GPU and on one rank; a gather between distinct
+ * GPUs over xGMI has not run on any machine yet. */
+int rma_gather_igg(rma_grid* g, const void* A, const int64_t size_A[3], const int64_t pitch_A[2],
+                   int elem_bytes, void* A_global, int root, void* stream);
+/* barrier-synchronised timers (the barrier's wait is bounded by
+ * RMA_COMM_TIMEOUT seconds, read once at rma_init_global_grid; default 300) */
 int rma_tic(rma_grid* g, void* stream);
 int rma_toc(rma_grid* g, void* stream, double* seconds);
 

@@ -221,6 +221,32 @@ void copy2d_batch_gpu(const Copy2d* copies, int n, int elem_bytes, stream_t stre
 void copy2d_batch_cpu(const Copy2d* copies, int n, int elem_bytes);
 
 // ---------------------------------------------------------------------------
+// Batched strided 3D block copy (blocks.hip): the pack (strided view -> dense
+// send buffer) and place (rank-major staging -> Cartesian A_global) primitive
+// of the C ABI's gather (rma/gather.h), and the device crop
+// Array(T[2:end-1,2:end-1]) of the reference scripts. Each block is nz planes
+// of ny rows of nx contiguous elements on both sides; pitches and extents in
+// elements, x fastest. Element size 4 or 8 bytes. A pitch along an extent of
+// 1 is never used and may be anything. Blocks of one call must not overlap in
+// dst. The GPU launcher splits n blocks into launches of <= kCopyBlocksBatch
+// descriptors of one access path (16-byte vectors when every row length, base
+// address and used pitch of the block is a multiple of 16 bytes, single
+// elements otherwise), in the order given. copy_blocks_cpu is the bitwise twin.
+// ---------------------------------------------------------------------------
+struct BlockCopy {
+  void* dst;
+  const void* src;
+  int64_t dst_row, dst_plane, src_row, src_plane;
+  int64_t nx, ny, nz;
+};
+constexpr int kCopyBlocksBatch = 32;  // 32 x 72 B of kernel arguments per launch
+// throws unless elem_bytes is 4 or 8, every pointer is set, every extent is
+// > 0 and every used pitch holds its extent (both twins call it before any work)
+void validate_block_copies(const BlockCopy* blocks, int64_t n, int elem_bytes);
+void copy_blocks_gpu(const BlockCopy* blocks, int64_t n, int elem_bytes, stream_t stream);
+void copy_blocks_cpu(const BlockCopy* blocks, int64_t n, int elem_bytes);
+
+// ---------------------------------------------------------------------------
 // Streaming roofline probes (same-box HBM ceiling for the T_eff comparison):
 //   copy : b[i] = a[i]              (1 read + 1 write)
 //   triad: c[i] = a[i] + s*b[i]     (2 reads + 1 write = the stencil's mix)

@@ -176,6 +176,40 @@ void copy2d_batch_cpu(const Copy2d* copies, int n, int elem_bytes) {
   }
 }
 
+void validate_block_copies(const BlockCopy* blocks, int64_t n, int elem_bytes) {
+  RMA_CHECK_ARG(elem_bytes == 4 || elem_bytes == 8,
+                "copy_blocks: unsupported elem_bytes " << elem_bytes << " (4 or 8)");
+  RMA_CHECK_ARG(n >= 0 && (n == 0 || blocks != nullptr), "copy_blocks: " << n << " blocks");
+  for (int64_t i = 0; i < n; ++i) {
+    const BlockCopy& c = blocks[i];
+    RMA_CHECK_ARG(c.dst && c.src, "copy_blocks: null pointer in block " << i);
+    RMA_CHECK_ARG(c.nx > 0 && c.ny > 0 && c.nz > 0,
+                  "copy_blocks: block " << i << " has extents " << c.nx << " x " << c.ny << " x "
+                                        << c.nz);
+    RMA_CHECK_ARG(c.ny == 1 || (c.dst_row >= c.nx && c.src_row >= c.nx),
+                  "copy_blocks: row pitch of block " << i << " smaller than nx=" << c.nx);
+    // a plane ends at its last row's last element
+    const int64_t dspan = (c.ny - 1) * (c.ny > 1 ? c.dst_row : 0) + c.nx;
+    const int64_t sspan = (c.ny - 1) * (c.ny > 1 ? c.src_row : 0) + c.nx;
+    RMA_CHECK_ARG(c.nz == 1 || (c.dst_plane >= dspan && c.src_plane >= sspan),
+                  "copy_blocks: plane pitch of block " << i << " smaller than a plane");
+  }
+}
+
+// CPU twin of copy_blocks_gpu (blocks.hip)
+void copy_blocks_cpu(const BlockCopy* blocks, int64_t n, int elem_bytes) {
+  validate_block_copies(blocks, n, elem_bytes);
+  for (int64_t i = 0; i < n; ++i) {
+    const BlockCopy& c = blocks[i];
+    char* d = static_cast<char*>(c.dst);
+    const char* s = static_cast<const char*>(c.src);
+    for (int64_t z = 0; z < c.nz; ++z)
+      for (int64_t y = 0; y < c.ny; ++y)
+        std::memcpy(d + (z * c.dst_plane + y * c.dst_row) * elem_bytes,
+                    s + (z * c.src_plane + y * c.src_row) * elem_bytes, (size_t)c.nx * elem_bytes);
+  }
+}
+
 double reduce_cpu(const double* A, int64_t n, int op) {
   double v = (op == kMax) ? -std::numeric_limits<double>::infinity()
                           : (op == kMin ? std::numeric_limits<double>::infinity() : 0.0);

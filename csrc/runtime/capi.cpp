@@ -14,6 +14,7 @@
 
 #include "rma/comm.h"
 #include "rma/executor.h"
+#include "rma/gather.h"
 #include "rma/halo.h"
 #include "rma/hip_check.h"
 #include "rma/kernels.h"
@@ -25,6 +26,10 @@ struct rma_grid : rma::GridDesc {  // host part: topology.cpp make_grid_desc
   std::unique_ptr<rma::RcclComm> comm;
   std::unique_ptr<rma::HaloExchanger> halo;
   std::chrono::steady_clock::time_point t0;
+  // RMA_COMM_TIMEOUT (s, default 300), read once at init: the bound of every
+  // blocking wait of this grid (tic / toc barriers, gather)
+  double comm_timeout = 300.0;
+  rma::GatherBuffers gather;  // device buffers of rma_gather_igg, grown on demand
   // executors hold raw pointers to `halo`: they pin the grid. finalize with
   // executors alive defers the teardown to the last rma_executor_destroy (a
   // GC'd host such as the Julia shim may finalize objects in any order), and
@@ -77,13 +82,15 @@ int rma_init_global_grid(int nx, int ny, int nz, const int dims[3], const int pe
     g->device = device;
     g->topo = std::make_unique<rma::CartTopology>(nprocs, g->dims, g->periods);
     RMA_HIP_CHECK(hipSetDevice(device));
+    const char* to = std::getenv("RMA_COMM_TIMEOUT");
+    const double timeout = to ? std::atof(to) : 300.0;
+    g->comm_timeout = timeout > 0 ? timeout : 300.0;
     if (nprocs > 1) {
       RMA_CHECK_ARG(unique_id != nullptr, "unique_id required when nprocs > 1");
       // non-blocking init with a timeout (RMA_COMM_TIMEOUT s, default 300)
       // unless RMA_RCCL_BLOCKING=1
       const char* tb = std::getenv("RMA_RCCL_BLOCKING");
-      const char* to = std::getenv("RMA_COMM_TIMEOUT");
-      const double init_timeout = (tb && tb[0] == '1') ? 0.0 : (to ? std::atof(to) : 300.0);
+      const double init_timeout = (tb && tb[0] == '1') ? 0.0 : timeout;
       g->comm = std::make_unique<rma::RcclComm>(nprocs, rank, std::string(unique_id, 128), device,
                                                 init_timeout);
     }
@@ -101,6 +108,7 @@ int rma_init_global_grid(int nx, int ny, int nz, const int dims[3], const int pe
 
 namespace {
 void destroy_grid(rma_grid* g) {
+  g->gather.release();
   g->halo.reset();
   g->comm.reset();
   delete g;
@@ -165,10 +173,19 @@ int rma_gather(rma_grid* g, const void* sendbuf, void* recvbuf, size_t bytes, in
   });
 }
 
+int rma_gather_igg(rma_grid* g, const void* A, const int64_t size_A[3], const int64_t pitch_A[2],
+                   int elem_bytes, void* A_global, int root, void* stream) {
+  return guard([&] {
+    RMA_CHECK_ARG(g != nullptr && !g->finalized, "gather: grid is NULL or finalized");
+    rma::gather_blocks(g->comm.get(), *g, g->comm_timeout, g->gather, A, size_A, pitch_A,
+                       elem_bytes, A_global, root, stream);
+  });
+}
+
 int rma_tic(rma_grid* g, void* stream) {
   return guard([&] {
     if (g->comm)
-      g->comm->barrier(stream, 300.0);
+      g->comm->barrier(stream, g->comm_timeout);
     else
       RMA_HIP_CHECK(hipStreamSynchronize(rma::as_stream(stream)));
     g->t0 = std::chrono::steady_clock::now();
@@ -178,7 +195,7 @@ int rma_tic(rma_grid* g, void* stream) {
 int rma_toc(rma_grid* g, void* stream, double* seconds) {
   return guard([&] {
     if (g->comm)
-      g->comm->barrier(stream, 300.0);
+      g->comm->barrier(stream, g->comm_timeout);
     else
       RMA_HIP_CHECK(hipStreamSynchronize(rma::as_stream(stream)));
     *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - g->t0).count();

@@ -20,7 +20,7 @@ module ImplicitGlobalGridMI355X
 
 using Libdl
 
-export init_global_grid, finalize_global_grid, update_halo!, gather!, nx_g, ny_g, nz_g,
+export init_global_grid, finalize_global_grid, update_halo!, gather!, gather_rankmajor!, nx_g, ny_g, nz_g,
        x_g, y_g, z_g, tic, toc, DiffusionExecutor, run!, current_field, check_executor
 
 const LIB = Ref{Ptr{Cvoid}}(C_NULL)
@@ -106,7 +106,21 @@ function update_halo!(A...; stream::Ptr{Cvoid}=C_NULL)
     return nothing
 end
 
+"""gather!(A, A_global; root=0): IGG's gather!. `root` assembles every rank's `A` at its
+Cartesian coordinates into `A_global` (size `dims .* size(A)`; `nothing` off-root). `A` and
+`A_global` may each be a host `Array` or a device array: the pointers pass straight
+through and the native side finds out which is which (rma_gather_igg). Blocking."""
 function gather!(A, A_global; root::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    sizes = Int64[size(A, 1), size(A, 2), size(A, 3)]
+    check(ccall(sym(:rma_gather_igg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                GRID[], devptr(A), sizes, C_NULL, sizeof(eltype(A)), devptr(A_global), root, stream))
+    return nothing
+end
+
+"""gather_rankmajor!(A, A_global; root=0): the rank-major concatenation of device buffers
+(rma_gather; what `gather!` did before it followed IGG's layout). Asynchronous on `stream`."""
+function gather_rankmajor!(A, A_global; root::Integer=0, stream::Ptr{Cvoid}=C_NULL)
     check(ccall(sym(:rma_gather), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint, Ptr{Cvoid}),
                 GRID[], pointer(A), A_global === nothing ? C_NULL : pointer(A_global),
                 sizeof(A), root, stream))

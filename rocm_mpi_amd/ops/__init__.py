@@ -6,6 +6,7 @@ from .stencil import (FAST5, KERNELS, KSTEP_CORE, LAB_KERNELS, PIPE, PIPE_MAX_K,
                       stencil_torch, stencilk_step, stream_handle, strip_cells, update,
                       validate_rects)
 from .halo_ops import copy_plane, copy_planes
+from .block_ops import assemble_blocks, copy_blocks
 
 __all__ = [
     "FAST5", "KERNELS", "KSTEP_CORE", "LAB_KERNELS", "PIPE", "PIPE_MAX_K", "Rect", "StencilCoef", "StencilTuning",
@@ -13,4 +14,5 @@ __all__ = [
     "hide_rects", "init_gaussian_", "init_random_", "interior_rect", "kernel_id", "kernel_name", "kp_views", "reduce",
     "residual", "stencil2_step", "stencil5_torch", "stencil_step", "stencil_torch",
     "stencilk_step", "stream_handle", "strip_cells", "update", "validate_rects", "copy_plane", "copy_planes",
+    "assemble_blocks", "copy_blocks",
 ]
