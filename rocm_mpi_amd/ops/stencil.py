@@ -514,7 +514,13 @@ _ws_cache: dict = {}
 
 
 def reduce(A: torch.Tensor, op: str = "sum") -> torch.Tensor:
-    """Device reduction of a float64 field -> 0-d float64 tensor (same device)."""
+    """Device reduction of a float64 field -> 0-d float64 tensor (same device).
+
+    The same semantics on every path (HIP kernel, C++ twin, torch fallback):
+    ``sum`` propagates NaN; ``max``, ``min`` and ``maxabs`` ignore NaN (fmax /
+    fmin) and return their identity (-inf, inf, 0) for a field with nothing
+    else in it; +inf and -inf count for them; ``nonfinite`` counts NaN and
+    +-inf cells. To find NaN use ``nonfinite`` (or ``sum``), never ``max``."""
     if op not in _RED:
         raise ValueError(f"op must be one of {sorted(_RED)}")
     if not (A.dtype == torch.float64 and A.is_contiguous()):
@@ -531,9 +537,16 @@ def reduce(A: torch.Tensor, op: str = "sum") -> torch.Tensor:
         return out
     if _use_native_cpu():
         return torch.tensor(native().reduce_cpu(_ptr(A), A.numel(), _RED[op]), dtype=torch.float64)
-    f = {"sum": torch.sum, "max": torch.max, "min": torch.min,
-         "maxabs": lambda a: a.abs().max(), "nonfinite": lambda a: (~torch.isfinite(a)).sum()}[op]
-    return f(A).to(torch.float64)
+    if op == "sum":
+        return torch.sum(A)
+    if op == "nonfinite":
+        return (~torch.isfinite(A)).sum().to(torch.float64)
+    # torch.max / torch.min propagate NaN, fmax / fmin do not: NaN cells take the identity
+    ident = {"max": -float("inf"), "min": float("inf"), "maxabs": 0.0}[op]
+    v = torch.where(torch.isnan(A), ident, A.abs() if op == "maxabs" else A)
+    if v.numel() == 0:
+        return torch.tensor(ident, dtype=torch.float64)
+    return v.min() if op == "min" else v.max()
 
 
 def field_stats(A: torch.Tensor) -> tuple[float, float, float]:
