@@ -128,6 +128,9 @@ def main(argv=None) -> int:
     ap.add_argument("--unit", default="auto",
                     help="translation unit (auto: the one holding the executor's kernel per K: "
                          "stencil_pipe_r20.hip / _r24.hip / _r.hip)")
+    ap.add_argument("--uniform", action="store_true",
+                    help="the uniform-factor variant (1/Cp one value, no factor rows) "
+                         "instead of the field path")
     ap.add_argument("--asm", default="", help="an existing .s instead of compiling")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
@@ -148,8 +151,10 @@ def main(argv=None) -> int:
         asm = a.asm or asms.setdefault(unit_of(K), compile_asm(
             unit_of(K), f"/tmp/isa_budget_{os.path.basename(unit_of(K))}.s"))
         lines = open(asm).read().splitlines()
-        # the plain instantiation (Dir = false; the direct-store variant is Lb1)
-        pref = f"_ZN3rma4pipe11pipe_kernelILi{K}ELi{a.S}ELi{a.V}ELi{ar}ELi1ELb0EE"
+        # the plain instantiation (Dir = false; the direct-store variant is Lb1),
+        # field path or uniform factor (Uni = false / true)
+        pref = (f"_ZN3rma4pipe11pipe_kernelILi{K}ELi{a.S}ELi{a.V}ELi{ar}ELi1ELb0E"
+                f"Lb{int(a.uniform)}EE")
         body = [ln for ln in lines]
         try:
             kb = kernel_body(body, pref)

@@ -63,6 +63,10 @@ def main(argv=None):
                     help="depths timed with the executor's own fast-math kernel and tuning "
                          "(native fast_kernel_k: ring kernel or piper, chunk rows); rows "
                          "kernel='exec' (the planner's cost table input, scripts/fit_pass_costs.py)")
+    ap.add_argument("--exec-uniform", dest="exec_uni", default="",
+                    help="depths timed like --exec but with the uniform-factor variant of the "
+                         "kernel (1/Cp is one value here; rows kernel='exec_uni'): the A/B of "
+                         "profiles/r7/uniform_factor.md")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
 
@@ -125,6 +129,7 @@ def main(argv=None):
     cfgs += [("pipe2", K, 0) for K in krange(a.pipe2)]
     cfgs += [("pipe5", K, 0) for K in krange(a.pipe5)]
     cfgs += [("exec", K, 0) for K in krange(a.exec_k)]
+    cfgs += [("exec_uni", K, 0) for K in krange(a.exec_uni)]
     for item in filter(None, a.kinds.split(",")):
         k, K, *c = item.split(":")  # kernel:K[:chunk_rows]
         cfgs.append((k, int(K), 0, int(c[0])) if c else (k, int(K), 0))
@@ -148,9 +153,10 @@ def main(argv=None):
             ops.stencil_step(T2, T, iCp, coef, rect, ops.StencilTuning())
         elif kind == "two_step":
             ops.stencil2_step(T2, T, iCp, coef, rect, ops.StencilTuning(chunk_rows=16, unroll=2))
-        elif kind == "exec":
+        elif kind in ("exec", "exec_uni"):
             kid, vec, ch = N.fast_kernel_k(K, n, tuple(coef))
-            tn = ops.StencilTuning(chunk_rows=ch, kernel=names[kid], vec=vec, xcd_remap=1)
+            tn = ops.StencilTuning(chunk_rows=ch, kernel=names[kid], vec=vec, xcd_remap=1,
+                                   uniform=kind == "exec_uni", uniform_value=1.0)
             ops.stencilk_step(K, T2, T, iCp, coef, rect, tn)
         else:
             vec = 2 if kind in ("lds_dpp", "fast5") else 5 if kind == "pipe5" else 4
@@ -183,12 +189,12 @@ def main(argv=None):
         cs, c = c[0], c[1:]
         kind, K, S = c[:3]
         med = statistics.median(times[(cs,) + c])
-        ek = (names[N.fast_kernel_k(K, n, tuple(coefs[cs]))[0]] if kind == "exec" else None)
+        ek = (names[N.fast_kernel_k(K, n, tuple(coefs[cs]))[0]] if kind in ("exec", "exec_uni") else None)
         rows.append({"coef_dims": cs, "ry": round(ops.fast5_constants(coefs[cs])[0], 6),
                      "kernel": kind, "exec_kernel": ek, "K": K, "stages": S or (native().pipe_default_stages(K)
                                                              if kind in ops.PIPE + ("pipe2", "pipe5")
                                                              else 0),
-                     "chunk_rows": (N.fast_kernel_k(K, n, tuple(coefs[cs]))[2] if kind == "exec"
+                     "chunk_rows": (N.fast_kernel_k(K, n, tuple(coefs[cs]))[2] if kind in ("exec", "exec_uni")
                                     else chunk(K, c[3] if len(c) > 3 else 0, kind)
                                     if kind not in ("march", "two_step") else None),
                      "vec": (N.pipe_vec(K, S, 0, n, 5, True) if kind == "pipe5" else None),

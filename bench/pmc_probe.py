@@ -43,11 +43,16 @@ if which == "piper":  # the executor's register-factor kernel alone (scheduler A
     K = int(os.environ.get("RMA_PROBE_K", "20"))
     ch = nat.pipe_chunk_rows(K, n, False) or nat.default_chunk_k(K, n)
     rect = [ops.interior_rect(n, n)]
+    # RMA_PROBE_KERNELS=piper_nosb: the K = 24 kernel; RMA_PROBE_UNIFORM=1: its
+    # uniform-factor variant (profiles/r7/uniform_factor.md)
+    kern = os.environ.get("RMA_PROBE_KERNELS", "piper").split(",")[0]
+    uni = os.environ.get("RMA_PROBE_UNIFORM", "0") == "1"
     for _ in range(reps):
         ops.stencilk_step(K, T2, T, iCp, c, rect,
-                          ops.StencilTuning(chunk_rows=ch, xcd_remap=1, kernel="piper", vec=4))
+                          ops.StencilTuning(chunk_rows=ch, xcd_remap=1, kernel=kern, vec=4,
+                                            uniform=uni, uniform_value=1.0))
     torch.cuda.synchronize()
-    print(f"probe done n={n} reps={reps} set={which} K={K} chunk={ch}")
+    print(f"probe done n={n} reps={reps} set={which} K={K} chunk={ch} kernel={kern} uniform={uni}")
     sys.exit(0)
 if which == "cols":  # piper with 1 vs 2 column waves per stage
     from rocm_mpi_amd._native import load_lab

@@ -153,10 +153,13 @@ PYBIND11_MODULE(_C, m) {
       "stencilk_rects",
       [](int K, uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny,
          const std::vector<Rect4>& rects, const Coef4& coef, int chunk_rows, int nontemporal,
-         uintptr_t stream, bool gpu, int xcd_remap, int vec, int kernel, int stages, int cols) {
+         uintptr_t stream, bool gpu, int xcd_remap, int vec, int kernel, int stages, int cols,
+         bool uniform, double uniform_value) {
         auto r = to_rects(rects);
         StencilTuning tn;
         tn.cols = cols;
+        tn.uniform = uniform;
+        tn.uniform_value = uniform_value;
         tn.chunk_rows = chunk_rows;
         tn.nontemporal = nontemporal;
         tn.xcd_remap = xcd_remap;
@@ -181,7 +184,8 @@ PYBIND11_MODULE(_C, m) {
       py::arg("K"), py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("ny"),
       py::arg("rects"), py::arg("coef"), py::arg("chunk_rows") = 16, py::arg("nontemporal") = 3,
       py::arg("stream") = 0, py::arg("gpu") = true, py::arg("xcd_remap") = -1,
-      py::arg("vec") = 2, py::arg("kernel") = 0, py::arg("stages") = 0, py::arg("cols") = 0);
+      py::arg("vec") = 2, py::arg("kernel") = 0, py::arg("stages") = 0, py::arg("cols") = 0,
+      py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
   m.def(
       "stream_copy",
       [](uintptr_t b, uintptr_t a, int64_t n, uintptr_t s, int nt, int blocks) {
@@ -568,6 +572,9 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("steps_done", &DiffusionExecutor::steps_done)
       .def_property_readonly("passes_done", &DiffusionExecutor::passes_done)
       .def_property_readonly("fused_passes", &DiffusionExecutor::fused_passes)
+      .def_property_readonly("uniform_factor", &DiffusionExecutor::uniform_factor)
+      .def("rescan_factor", &DiffusionExecutor::rescan_factor,
+           py::call_guard<py::gil_scoped_release>())
       .def("check_error", &DiffusionExecutor::check_error)
       .def("plan", &DiffusionExecutor::plan, py::arg("nsteps"))
       .def_property_readonly("pass_costs", &DiffusionExecutor::pass_costs)

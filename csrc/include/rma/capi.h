@@ -94,7 +94,13 @@ int rma_fill(double* A, int64_t n, double value, void* stream);
 
 /* native time-loop executor: mode 0 = perf (fused), 1 = perf_hide (boundary on a
  * high-priority stream + halo exchange overlapped with the interior), 2 = kp
- * (needs qx, qy, dTdt). Enqueues n steps after the work on `stream`. */
+ * (needs qx, qy, dTdt). Enqueues n steps after the work on `stream`.
+ * iCp (1/Cp) is EXAMINED WHEN THE EXECUTOR IS CREATED (after a device
+ * synchronisation): where every cell holds bit-for-bit one value, the
+ * fast-math K-step passes take that value as a kernel argument and no longer
+ * read the array (16 instead of 24 bytes per cell and pass, the same results).
+ * After writing to iCp, destroy the executor and create a new one; an
+ * executor that found a uniform array does not see later changes. */
 typedef struct rma_executor rma_executor;
 int rma_executor_create(rma_grid* g, int mode, double* T, double* T2, const double* iCp,
                         int64_t nx, int64_t ny, const double coef[4], int64_t bwx, int64_t bwy,

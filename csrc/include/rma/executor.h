@@ -121,6 +121,19 @@ class DiffusionExecutor {
   // throws if a fused pass's bounded wait for its frame flag timed out (the
   // halos of that pass are wrong); also checked at every run() and timings()
   void check_error() const { check_fused_error(); }
+  // Uniform 1/Cp. The constructor reads the 1/Cp array once on the device
+  // (count_differing_gpu, on the executor's own stream): when every cell has
+  // bit-for-bit the value of cell 0, the K-step passes whose kernel has a
+  // uniform-factor variant (register-factor pipelined kernels, 2 or 4 cells
+  // per lane, no direct stores) take that value as an argument and do not
+  // stream the array: 16 instead of 24 bytes per cell and pass, the same bits.
+  // The verdict is NOT re-examined by run(): after writing to 1/Cp call
+  // rescan_factor() (or build a new executor) before the next run().
+  // RMA_DIAG uniform_factor=off keeps the verdict false.
+  bool uniform_factor() const { return uniform_; }
+  // synchronises both streams, rescans, drops a captured graph if the verdict
+  // or the value changed; returns the verdict
+  bool rescan_factor();
   // Direct-store halos (kernels.h DirectStores), replacing the exchange: every
   // pass's pipelined kernel also stores the cells that are a neighbour's halo
   // straight into that neighbour's output field. peers[d] for the 8
@@ -175,6 +188,9 @@ class DiffusionExecutor {
   void build_graph(int64_t steps, int reps);
   void run_eager(int64_t nsteps);
   bool fast5() const;
+  void scan_factor();
+  bool uniform_ = false;  // 1/Cp is the one value c0_ (scan_factor)
+  double c0_ = 0.0;
 
   double* T_;
   double* T2_;

@@ -71,6 +71,15 @@ struct StencilTuning {
   int signal_chunk_rows = 0;  // rows per task of the signal rects (0: chunk_rows)
   // direct-store halos of this launch (pipelined kernels; nullptr: none)
   const DirectStores* direct = nullptr;
+  // 1/Cp is bit-for-bit the one value uniform_value in every cell (the caller
+  // vouches for it; DiffusionExecutor scans the array): the register-factor
+  // pipelined kernels (12 / 22) at 2 or 4 cells per lane then run their
+  // uniform-factor variant, which does not read the array (16 instead of 24
+  // bytes per cell and pass), bitwise equal to the field path. Launches the
+  // variant does not cover (1 cell per lane, direct stores, other kernels)
+  // run the field path.
+  bool uniform = false;
+  double uniform_value = 0.0;
 };
 
 void stencil_rects_gpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
@@ -143,6 +152,13 @@ void stencil5_rects_cpu(double* T2, const double* T, const double* iCp, int64_t 
                         const Rect* rects, int nrects, const StencilCoef& c);
 void stencilk5_rects_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
                          int64_t ny, const Rect* rects, int nrects, const StencilCoef& c);
+
+// Cells of A[0, n) whose 64-bit pattern differs from A[0]'s (-0.0 differs from
+// 0.0, NaN payloads count), for DiffusionExecutor's uniform-1/Cp verdict. GPU:
+// out[0] += the count (zero it on the same stream first), out[1] = A[0]'s bits;
+// device memory, no synchronisation. The host twin returns the count.
+void count_differing_gpu(const double* A, int64_t n, uint64_t* out2, stream_t stream);
+int64_t count_differing_cpu(const double* A, int64_t n);
 
 // Width (in cells) of one wave's x-strip in the march kernel; perf_hide rounds
 // its x-frame so the interior rect starts on a strip boundary.

@@ -227,6 +227,27 @@ double reduce_cpu(const double* A, int64_t n, int op) {
   return v;
 }
 
+// CPU twin of count_differing_gpu (misc.hip): bit patterns, not values
+int64_t count_differing_cpu(const double* A, int64_t n) {
+  int64_t cnt = 0;
+  uint64_t first = 0, v = 0;
+  if (n > 0) std::memcpy(&first, A, sizeof first);
+  for (int64_t i = 0; i < n; ++i) {
+    std::memcpy(&v, A + i, sizeof v);
+    cnt += v != first ? 1 : 0;
+  }
+  return cnt;
+}
+
+// Host builds of the runtime without device code (the sanitizer programs of
+// tests/native, where "device" memory is host memory) resolve the launch to
+// this twin; in the core library the definition of misc.hip takes its place.
+__attribute__((weak)) void count_differing_gpu(const double* A, int64_t n, uint64_t* out2,
+                                               stream_t) {
+  out2[0] += (uint64_t)count_differing_cpu(A, n);
+  std::memcpy(&out2[1], A, sizeof(uint64_t));
+}
+
 // CPU twin of field_stats_gpu (misc.hip)
 void field_stats_cpu(const double* A, int64_t n, double* out3) {
   double bad = 0.0, lo = INFINITY, hi = -INFINITY;

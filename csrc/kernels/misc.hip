@@ -202,6 +202,19 @@ __global__ __launch_bounds__(kRedBlock) void reduce_stage2(const double* __restr
   if (threadIdx.x == 0) *out = v;
 }
 
+// Cells whose 64-bit pattern differs from cell 0's (count_differing_gpu): one
+// read of the array, a per-thread count, one atomic per thread that found any.
+__global__ __launch_bounds__(kRedBlock) void count_differing_kernel(
+    const unsigned long long* __restrict__ A, int64_t n, unsigned long long* __restrict__ out2) {
+  const unsigned long long first = A[0];
+  unsigned long long cnt = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    cnt += A[i] != first ? 1u : 0u;
+  if (cnt) atomicAdd(out2, cnt);
+  if (blockIdx.x == 0 && threadIdx.x == 0) out2[1] = first;
+}
+
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 
 // One-pass field statistics (bench.py full-field check): non-finite count, min
@@ -515,6 +528,16 @@ void field_stats_gpu(const double* A, int64_t n, double* out3, double* workspace
   field_stats_stage1<<<(unsigned)nb, kRedBlock, 0, s>>>(A, n, workspace);
   RMA_HIP_LAUNCH_CHECK();
   field_stats_stage2<<<1, kRedBlock, 0, s>>>(workspace, (int)nb, out3);
+  RMA_HIP_LAUNCH_CHECK();
+}
+
+void count_differing_gpu(const double* A, int64_t n, uint64_t* out2, stream_t stream) {
+  RMA_CHECK_ARG(n >= 1, "count_differing of an empty field");
+  int64_t nb = (n + kRedBlock * 8 - 1) / (kRedBlock * 8);
+  nb = nb < 1 ? 1 : (nb > kStatsBlocks ? kStatsBlocks : nb);
+  count_differing_kernel<<<(unsigned)nb, kRedBlock, 0, as_stream(stream)>>>(
+      reinterpret_cast<const unsigned long long*>(A), n,
+      reinterpret_cast<unsigned long long*>(out2));
   RMA_HIP_LAUNCH_CHECK();
 }
 

@@ -155,35 +155,45 @@ constexpr int waves_per_simd() {
 // 17..20): H = 6 (K >= 21) spills 39 VGPRs at K=24, and H = 4 (K = 13..16)
 // takes 214 instead of 161 VGPRs at K=16 (2 instead of 3 waves per SIMD);
 // K=20: 247 instead of 201 VGPRs, no spill, still 2 waves per SIMD.
-template <int K, int S, int Ar>
+//
+// Uniform factor (Uni): 1/Cp is one value, passed as a kernel argument. No
+// factor rows at all (no 1/Cp stream, no shift register, no factor hand-off):
+// every level's factor is g = gs * c0 inside the interior and 0.0 outside, a
+// scalar select per level. Without factor rows nothing outlives the 3-row
+// window rotation, so the row loop unrolled by 3 has no back-edge moves.
+template <int K, int S, int Ar, bool Uni = false>
 constexpr bool pipe_u6() {
-  return ar_reg(Ar) && Plan<K, S>::H == 5;
+  return ar_reg(Ar) && !Uni && Plan<K, S>::H == 5;
 }
 // LDS-DMA staging rows per array: one per phase of the unrolled row loop, so
 // a row DMA'd at phase p is read at phase p of the next loop trip (across the
 // back edge: a read of a slot DMA'd earlier in the same trip gets a vmcnt(0)
 // from the compiler's LDS-DMA hazard check, which drains the prefetch)
-template <int K, int S, int Ar>
+template <int K, int S, int Ar, bool Uni = false>
 constexpr int staging_rows() {
-  return pipe_u6<K, S, Ar>() ? 6 : 3;
+  return pipe_u6<K, S, Ar, Uni>() ? 6 : 3;
 }
 // T + factor hand-off rows (block-wide, WB columns), LDS-DMA staging (V = 2, 4;
-// private to each column's stage-0 wave, W columns each)
-template <int K, int S, int V, int Ar, int C = 1>
+// private to each column's stage-0 wave, W columns each). Uniform factor: the T
+// rows only, of both.
+template <int K, int S, int V, int Ar, int C = 1, bool Uni = false>
 constexpr int lds_bytes_reg() {
-  return (4 * (S > 1 ? S - 1 : 1) * Geo<K, S, V, C>::WB +
-          (V == 2 || V == 4 ? 2 * staging_rows<K, S, Ar>() * Geo<K, S, V, C>::W * C : 0)) *
+  return ((Uni ? 2 : 4) * (S > 1 ? S - 1 : 1) * Geo<K, S, V, C>::WB +
+          (V == 2 || V == 4
+               ? (Uni ? 1 : 2) * staging_rows<K, S, Ar, Uni>() * Geo<K, S, V, C>::W * C
+               : 0)) *
              8 +
          8;
 }
-template <int K, int S, int V, int Ar, int C>
+template <int K, int S, int V, int Ar, int C, bool Uni = false>
 constexpr int kernel_waves() {
   if constexpr (ar_reg(Ar)) {
-    // + the H factor rows (measured 158 / 233 / 256 VGPRs at K = 12 / 20 / 24, V = 4)
+    // + the H factor rows (measured 158 / 233 / 256 VGPRs at K = 12 / 20 / 24, V = 4);
+    // uniform factor: none
     constexpr int H = Plan<K, S>::H;
-    constexpr int vgpr = 8 * H * V + 8 * V + 40;
+    constexpr int vgpr = (Uni ? 6 : 8) * H * V + 8 * V + 40;
     constexpr int by_vgpr = 512 / ((vgpr + 7) / 8 * 8);
-    constexpr int w = occupancy<K, S, V, false, C>(lds_bytes_reg<K, S, V, Ar, C>());
+    constexpr int w = occupancy<K, S, V, false, C>(lds_bytes_reg<K, S, V, Ar, C, Uni>());
     return by_vgpr < 2 ? 2 : (by_vgpr < w ? by_vgpr : w);
   } else {
     return waves_per_simd<K, S, V, Ar == kArCanon, C>();
@@ -234,11 +244,11 @@ __device__ __forceinline__ void direct_row(const DirectStores& D, int row, int64
   if (dxp) xside(4, 2, 7, -sx, D.xp0, D.xp1);   // (+1, 0), (+1, -1), (+1, +1)
 }
 
-template <int K, int S, int V, int Ar, int C, bool Dir>
+template <int K, int S, int V, int Ar, int C, bool Dir, bool Uni>
 __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double* __restrict__ T,
                                           const double* __restrict__ iCp, int64_t nx, int64_t ny,
                                           const RectList& L, const StencilCoef& k, int chunk_rows,
-                                          int remap, const DirectStores& DS) {
+                                          int remap, const DirectStores& DS, double c0) {
   using P = Plan<K, S>;
   constexpr bool Canon = Ar == kArCanon, kRegG = ar_reg(Ar);
   static_assert(!kRegG || (V != 5 && (C == 1 || V == 4)),
@@ -252,8 +262,11 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // s_barrier after lgkmcnt(0): __syncthreads() would also wait vmcnt(0) and
   // drain the prefetch every row.
   constexpr bool kGlds = kRegG && (V == 2 || V == 4);
-  constexpr bool kU6 = pipe_u6<K, S, Ar>();
-  constexpr int NST = staging_rows<K, S, Ar>();  // staging rows per array
+  static_assert(!Uni || (kGlds && C == 1 && !Dir),
+                "uniform factor: register factors, 2 or 4 cells per lane, one column wave, "
+                "no direct stores");
+  constexpr bool kU6 = pipe_u6<K, S, Ar, Uni>();
+  constexpr int NST = staging_rows<K, S, Ar, Uni>();  // staging rows per array
   using G = Geo<K, S, V, C>;
   constexpr int H = P::H, HL = P::HL, R = ring_rows<K, S, V>();
   constexpr int M = kRegG ? 0 : mirror_rows<K, S, V, Canon, C>();
@@ -360,10 +373,12 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // only, so other instantiations allocate nothing for it): the compiler's
   // LDS-DMA hazard check then sees the hand-off writes and the DMA on distinct
   // objects and waits for no DMA before them
-  constexpr int kRing = kRegG ? 1 : (R + M) * WB, kHand = kRegG ? 4 : 2;
+  // (uniform factor: T hand-off rows and T staging rows only)
+  constexpr int kRing = kRegG ? 1 : (R + M) * WB, kHand = kRegG && !Uni ? 4 : 2;
+  constexpr int kStgArrays = Uni ? 1 : 2;
   __shared__ double ring[kRing];
   __shared__ double hand[kHand][NH][WB];
-  __shared__ double staging[kGlds ? 2 * NST * W * C : 1];  // per column wave
+  __shared__ double staging[kGlds ? kStgArrays * NST * W * C : 1];  // per column wave
   if constexpr (!kRegG)
     for (int t = threadIdx.x; t < kRing; t += S * C * kWave) ring[t] = 0.0;
   for (int t = threadIdx.x; t < kHand * NH * WB; t += S * C * kWave) (&hand[0][0][0])[t] = 0.0;
@@ -373,15 +388,16 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // register allocator a few row copies per 3 rows (the row loop stays
   // unrolled by 3: unrolling by 6 for static names raised the VGPR count of
   // the plain kernel from 213 to 270)
-  double gr[kRegG ? H : 1][V];
+  constexpr int NG = kRegG && !Uni ? H : 1;
+  double gr[NG][V];
 #pragma unroll
-  for (int q = 0; q < (kRegG ? H : 1); ++q)
+  for (int q = 0; q < NG; ++q)
 #pragma unroll
     for (int v = 0; v < V; ++v) gr[q][v] = 0.0;
-  auto gh = [&](int pb, int st) { return &hand[2 + pb][st][0]; };
+  auto gh = [&](int pb, int st) { return &hand[(kHand - 2) + pb][st][0]; };
   auto gshift = [&]() {
 #pragma unroll
-    for (int q = (kRegG ? H : 1) - 1; q > 0; --q)
+    for (int q = NG - 1; q > 0; --q)
 #pragma unroll
       for (int v = 0; v < V; ++v) gr[q][v] = gr[q - 1][v];
   };
@@ -390,7 +406,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // the column wave's own (only its stage-0 wave writes and reads it):
   // instruction h, lane l loads the cell pair 2l+h of the lane's window, which
   // lands at dbl2 slot h*64 + l (the one-window layout rds reads)
-  auto stg = [&](int a, int r) { return &staging[((2 * col + a) * NST + r) * W]; };
+  auto stg = [&](int a, int r) { return &staging[((kStgArrays * col + a) * NST + r) * W]; };
   auto glds_row = [&](int a, int y, int r) {
     const double* rb = (a ? iCp : T) + rowc(y) * nx;
 #pragma unroll
@@ -402,7 +418,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
 #pragma unroll
       for (int r = 0; r < NST; ++r) {
         glds_row(0, i + 1 + r, r);
-        glds_row(1, i + r, r);
+        if constexpr (!Uni) glds_row(1, i + r, r);
       }
     }
   }
@@ -458,8 +474,19 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   for (int v = 0; v < V; ++v) gp[v] = 0.0;
   int par = 0;
   const int lag = stage * (H + 1);  // rows behind stage 0
+  // uniform factor: g = gs * c0 (the field path's one multiply) as two scalars,
+  // so a level's row test selects it on the scalar unit and the last fma of a
+  // cell takes it as its scalar operand; gc: the same with the x-boundary
+  // columns zeroed, for the windows that hold one (!xin)
+  const double gU = gs * c0;
+  const int gUlo = __builtin_amdgcn_readfirstlane(__double2loint(gU));
+  const int gUhi = __builtin_amdgcn_readfirstlane(__double2hiint(gU));
+  double gc[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) gc[v] = cin[v] ? gU : 0.0;
 
-  auto iter = [&](auto Pc, auto S0c, auto LASTc) {
+  auto iter = [&](auto Pc, auto S0c, auto LASTc, auto XINc) {
+    constexpr bool XIN = decltype(XINc)::value;  // uniform factor: no x-boundary cell
     constexpr int Ps = decltype(Pc)::value;  // phase of the unrolled loop (staging slot)
     constexpr int Pr = Ps % 3;                // phase of the 3-row windows w
     constexpr bool S0 = decltype(S0c)::value;
@@ -470,7 +497,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
     if constexpr (S0) {
       // register factors: retire level H's row to stage 1 before row i's
       // factors exist (one factor row fewer live)
-      if constexpr (kRegG && !LAST) wr2(gh(par, 0), gr[H - 1]);
+      if constexpr (kRegG && !Uni && !LAST) wr2(gh(par, 0), gr[NG - 1]);
       const bool rin1 = i >= 1 && i <= ny32 - 2;
       if constexpr (kGlds) {
         // NST (3, or 6 when unrolled by 6) rows ahead: the staging slot of this
@@ -484,23 +511,25 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
         // before it). The builtin (gfx9 encoding: vmcnt bits 3:0 and 15:14,
         // expcnt 6:4 and lgkmcnt 11:8 at their maxima = no wait) plus an empty
         // asm keeps the reads below the wait.
-        constexpr int kVm = (NST - 1) * V;
+        constexpr int kVm = (NST - 1) * kStgArrays * (V / 2);
         static_assert(kVm < 64, "vmcnt");
         __builtin_amdgcn_s_waitcnt(0x0F70 | (kVm & 15) | ((kVm >> 4) << 14));
         asm volatile("" ::: "memory");
         rds(stg(0, Ps), pT);
-        rds(stg(1, Ps), pC);
+        if constexpr (!Uni) rds(stg(1, Ps), pC);
       }
 #pragma unroll
       for (int v = 0; v < V; ++v) w[0][Pr][v] = pT[v];
-      if (rin1 && xin) {  // wave-uniform: no per-cell selects away from the x edges
+      if constexpr (Uni) {  // the levels select their factor themselves
+      } else if (rin1 && xin) {  // wave-uniform: no per-cell selects away from the x edges
 #pragma unroll
         for (int v = 0; v < V; ++v) g[v] = Canon ? pC[v] : gs * pC[v];
       } else {
 #pragma unroll
         for (int v = 0; v < V; ++v) g[v] = (rin1 && cin[v]) ? (Canon ? pC[v] : gs * pC[v]) : 0.0;
       }
-      if constexpr (kRegG) {  // shift, take row i
+      if constexpr (Uni) {
+      } else if constexpr (kRegG) {  // shift, take row i
         gshift();
 #pragma unroll
         for (int v = 0; v < V; ++v) gr[0][v] = g[v];
@@ -527,8 +556,8 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
       }
     } else {
       rd2(&hand[par ^ 1][stage - 1][0], w[0][Pr]);
-      if constexpr (kRegG) {
-        if constexpr (!LAST) wr2(gh(par, stage), gr[H - 1]);
+      if constexpr (kRegG && !Uni) {
+        if constexpr (!LAST) wr2(gh(par, stage), gr[NG - 1]);
         gshift();
         rd2(gh(par ^ 1, stage - 1), gr[0]);
       }
@@ -574,7 +603,17 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
     for (int j = 1; j <= NL; ++j) {
       const int row = i - (S0 ? 0 : lag) - (j - 1);
       double gl[V];
-      if constexpr (kRegG) {
+      if constexpr (Uni) {
+        const bool rin = row >= 1 && row <= ny32 - 2;  // wave-uniform
+        if constexpr (XIN) {
+          const double gu = __hiloint2double(rin ? gUhi : 0, rin ? gUlo : 0);
+#pragma unroll
+          for (int v = 0; v < V; ++v) gl[v] = gu;
+        } else {
+#pragma unroll
+          for (int v = 0; v < V; ++v) gl[v] = rin ? gc[v] : 0.0;
+        }
+      } else if constexpr (kRegG) {
 #pragma unroll
         for (int v = 0; v < V; ++v) gl[v] = gr[j - 1][v];
       } else {
@@ -665,7 +704,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
         __builtin_amdgcn_s_waitcnt(0xC07F);
         asm volatile("" ::: "memory");
         glds_row(0, i + 1 + NST, Ps);
-        glds_row(1, i + NST, Ps);
+        if constexpr (!Uni) glds_row(1, i + NST, Ps);
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     } else {
@@ -675,33 +714,45 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // one row loop per stage role (stage is wave-uniform; every copy passes the
   // same barriers): stage 0 carries the HBM prefetch registers, the others not
   // unrolled by 6 where the factor rows live 5 iterations (pipe_u6), else 3
-  auto run = [&](auto S0c, auto LASTc) {
+  auto run = [&](auto S0c, auto LASTc, auto XINc) {
     for (;;) {
-      iter(std::integral_constant<int, 0>{}, S0c, LASTc);
+      iter(std::integral_constant<int, 0>{}, S0c, LASTc, XINc);
       if (++i > iend) break;
-      iter(std::integral_constant<int, 1>{}, S0c, LASTc);
+      iter(std::integral_constant<int, 1>{}, S0c, LASTc, XINc);
       if (++i > iend) break;
-      iter(std::integral_constant<int, 2>{}, S0c, LASTc);
+      iter(std::integral_constant<int, 2>{}, S0c, LASTc, XINc);
       if (++i > iend) break;
       if constexpr (kU6) {
-        iter(std::integral_constant<int, 3>{}, S0c, LASTc);
+        iter(std::integral_constant<int, 3>{}, S0c, LASTc, XINc);
         if (++i > iend) break;
-        iter(std::integral_constant<int, 4>{}, S0c, LASTc);
+        iter(std::integral_constant<int, 4>{}, S0c, LASTc, XINc);
         if (++i > iend) break;
-        iter(std::integral_constant<int, 5>{}, S0c, LASTc);
+        iter(std::integral_constant<int, 5>{}, S0c, LASTc, XINc);
         if (++i > iend) break;
       }
     }
   };
-  if constexpr (S == 1) {
-    run(std::true_type{}, std::true_type{});
+  // (uniform factor: a second copy for the windows that hold an x-boundary
+  // column, two strips of a tile, so that the others carry no per-cell select)
+  auto role = [&](auto XINc) {
+    if constexpr (S == 1) {
+      run(std::true_type{}, std::true_type{}, XINc);
+    } else {
+      if (stage == 0)
+        run(std::true_type{}, std::false_type{}, XINc);
+      else if (stage == S - 1)
+        run(std::false_type{}, std::true_type{}, XINc);
+      else if constexpr (S > 2)
+        run(std::false_type{}, std::false_type{}, XINc);
+    }
+  };
+  if constexpr (Uni) {
+    if (xin)
+      role(std::true_type{});
+    else
+      role(std::false_type{});
   } else {
-    if (stage == 0)
-      run(std::true_type{}, std::false_type{});
-    else if (stage == S - 1)
-      run(std::false_type{}, std::true_type{});
-    else if constexpr (S > 2)
-      run(std::false_type{}, std::false_type{});
+    role(std::true_type{});
   }
   // the staging DMA issued past the last row must land before the block's LDS
   // is released to the next block on this CU
@@ -716,15 +767,16 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
 // task measured when every task of a pass ran it, K = 20 then at one wave
 // per SIMD), so the plain kernels carry none of it and the executor gives the
 // Dir variant the frame launches only, which hold every image cell.
-template <int K, int S, int V, int Ar, int C, bool Dir = false>
+// Uni: the uniform-factor variant (c0 = the one value of 1/Cp; iCp is not read).
+template <int K, int S, int V, int Ar, int C, bool Dir = false, bool Uni = false>
 __global__ __launch_bounds__(kWave * S * C) __attribute__((amdgpu_waves_per_eu(
-    kernel_waves<K, S, V, Ar, C>()))) void pipe_kernel(double* __restrict__ T2,
-                                                      const double* __restrict__ T,
-                                                      const double* __restrict__ iCp,
-                                                      int64_t nx, int64_t ny, RectList L,
-                                                      StencilCoef k, int chunk_rows,
-                                                      int remap, DirectStores D) {
-  pipe_body<K, S, V, Ar, C, Dir>(T2, T, iCp, nx, ny, L, k, chunk_rows, remap, D);
+    kernel_waves<K, S, V, Ar, C, Uni>()))) void pipe_kernel(double* __restrict__ T2,
+                                                           const double* __restrict__ T,
+                                                           const double* __restrict__ iCp,
+                                                           int64_t nx, int64_t ny, RectList L,
+                                                           StencilCoef k, int chunk_rows,
+                                                           int remap, DirectStores D, double c0) {
+  pipe_body<K, S, V, Ar, C, Dir, Uni>(T2, T, iCp, nx, ny, L, k, chunk_rows, remap, D, c0);
 }
 
 // direct-store variants exist for the production fast-math arithmetics
@@ -732,6 +784,13 @@ __global__ __launch_bounds__(kWave * S * C) __attribute__((amdgpu_waves_per_eu(
 template <int V, int Ar, int C>
 constexpr bool has_direct() {
   return C == 1 && V != 5 && (Ar == kArFast5 || Ar == kArFast5Reg || Ar == kArFast5RegNoSB);
+}
+
+// uniform-factor variants: the register-factor arithmetics at 2 or 4 cells per
+// lane, one column wave, in the units that ask for them (RMA_PIPE_CASE_U)
+template <int V, int Ar, int C>
+constexpr bool has_uniform() {
+  return C == 1 && (V == 2 || V == 4) && (Ar == kArFast5Reg || Ar == kArFast5RegNoSB);
 }
 
 struct PipeLaunch {
@@ -750,11 +809,13 @@ struct PipeLaunch {
   const DirectStores* direct = nullptr;  // direct-store halos (nullptr: none)
   int* occupancy = nullptr;  // non-null: launch nothing, store the blocks per CU of the
                              // plain kernel [0] and of its direct-store variant [1] (0: none)
+  int uniform = 0;  // 1/Cp is the one value c0: run the uniform-factor variant where the
+  double c0 = 0.0;  // instantiation has one and the launch stores no halos directly
 };
 
 // Plans the (strip, chunk) tasks with this instantiation's block width
 // (Geo::WB, kStep), so host planning and kernel geometry cannot disagree.
-template <int K, int S, int V, int Ar, int C = 1>
+template <int K, int S, int V, int Ar, int C = 1, bool WithUni = false>
 void launch(const PipeLaunch& a) {
   if (a.occupancy) {
     const int bs = kWave * S * C;
@@ -789,15 +850,22 @@ void launch(const PipeLaunch& a) {
   if (a.direct && a.direct->on) {
     if constexpr (has_direct<V, Ar, C>()) {
       pipe_kernel<K, S, V, Ar, C, true><<<grid, block, 0, a.stream>>>(
-          a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, *a.direct);
+          a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, *a.direct, 0.0);
     } else {
       RMA_CHECK_ARG(false, "no direct-store variant of the pipelined kernel K=" << K << " S=" << S
                                 << " V=" << V << " arithmetic " << Ar << " columns " << C);
     }
     return;
   }
-  pipe_kernel<K, S, V, Ar, C><<<grid, block, 0, a.stream>>>(a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k,
-                                                           a.chunk_rows, a.remap, DirectStores{});
+  if constexpr (WithUni && has_uniform<V, Ar, C>()) {
+    if (a.uniform) {
+      pipe_kernel<K, S, V, Ar, C, false, true><<<grid, block, 0, a.stream>>>(
+          a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, a.c0);
+      return;
+    }
+  }
+  pipe_kernel<K, S, V, Ar, C><<<grid, block, 0, a.stream>>>(
+      a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, 0.0);
 }
 
 // Each stencil_pipe_{a,b,c}.hip unit instantiates a range of (K, S) of the
@@ -823,6 +891,15 @@ bool dispatch_r24(int K, int S, int V, int ar, const PipeLaunch& a);
   if (K == KK && S == SS && ar == CC) {                            \
     if (V == 4) launch<KK, SS, 4, CC>(a);                          \
     else if (V == 2) launch<KK, SS, 2, CC>(a);                     \
+    else launch<KK, SS, 1, CC>(a);                                 \
+    return true;                                                   \
+  }
+
+// ... with the uniform-factor variants (register factors; V = 1 has none)
+#define RMA_PIPE_CASE_U(KK, SS, CC)                                \
+  if (K == KK && S == SS && ar == CC) {                            \
+    if (V == 4) launch<KK, SS, 4, CC, 1, true>(a);                 \
+    else if (V == 2) launch<KK, SS, 2, CC, 1, true>(a);            \
     else launch<KK, SS, 1, CC>(a);                                 \
     return true;                                                   \
   }

@@ -88,6 +88,12 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
     }
     a.direct = &D;
   }
+  // uniform 1/Cp: the variant exists without direct stores only (launch<> falls
+  // back to the field path where the instantiation has none, e.g. V = 1)
+  if (tune.uniform && !a.direct) {
+    a.uniform = 1;
+    a.c0 = tune.uniform_value;
+  }
   if (tune.signal || tune.signal_rects > 0) {  // lead rects (with or without the signal)
     RMA_CHECK_ARG(tune.signal_rects >= 1 && tune.signal_rects < nrects,
                   "signal rects " << tune.signal_rects << " of " << nrects);

@@ -15,21 +15,21 @@ namespace pipe {
 
 bool dispatch_r(int K, int S, int V, int ar, const PipeLaunch& a) {
   if (ar != kArFast5Reg) return false;
-  RMA_PIPE_CASE(10, 4, kArFast5Reg)
-  RMA_PIPE_CASE(11, 4, kArFast5Reg)
-  RMA_PIPE_CASE(12, 4, kArFast5Reg)
-  RMA_PIPE_CASE(13, 4, kArFast5Reg)
-  RMA_PIPE_CASE(14, 4, kArFast5Reg)
-  RMA_PIPE_CASE(15, 4, kArFast5Reg)
-  RMA_PIPE_CASE(16, 4, kArFast5Reg)
-  RMA_PIPE_CASE(17, 4, kArFast5Reg)
-  RMA_PIPE_CASE(18, 4, kArFast5Reg)
-  RMA_PIPE_CASE(19, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(10, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(11, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(12, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(13, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(14, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(15, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(16, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(17, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(18, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(19, 4, kArFast5Reg)
   // K = 20: stencil_pipe_r20.hip
-  RMA_PIPE_CASE(21, 4, kArFast5Reg)
-  RMA_PIPE_CASE(22, 4, kArFast5Reg)
-  RMA_PIPE_CASE(23, 4, kArFast5Reg)
-  RMA_PIPE_CASE(24, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(21, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(22, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(23, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(24, 4, kArFast5Reg)
   return false;
 }
 

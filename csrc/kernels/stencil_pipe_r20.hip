@@ -12,7 +12,7 @@ namespace pipe {
 
 bool dispatch_r20(int K, int S, int V, int ar, const PipeLaunch& a) {
   if (ar != kArFast5Reg) return false;
-  RMA_PIPE_CASE(20, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U(20, 4, kArFast5Reg)
   return false;
 }
 

@@ -12,7 +12,7 @@ namespace pipe {
 
 bool dispatch_r24(int K, int S, int V, int ar, const PipeLaunch& a) {
   if (ar != kArFast5RegNoSB) return false;
-  RMA_PIPE_CASE(24, 4, kArFast5RegNoSB)
+  RMA_PIPE_CASE_U(24, 4, kArFast5RegNoSB)
   return false;
 }
 

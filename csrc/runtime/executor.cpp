@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -234,6 +235,7 @@ DiffusionExecutor::DiffusionExecutor(double* T, double* T2, const double* iCp, i
       RMA_HIP_CHECK(
           hipHostGetDevicePointer(reinterpret_cast<void**>(&ferr_dev_), ferr_host_, 0));
     }
+    scan_factor();  // before prime(): it launches the variant the passes will run
     if (!diag_flag("no_prime")) prime();
   } catch (...) {
     release_resources();
@@ -271,6 +273,49 @@ void DiffusionExecutor::release_resources() {
     if (s_lo_) (void)hipStreamDestroy(S(s_lo_));
   }
   s_hi_ = s_lo_ = nullptr;
+}
+
+void DiffusionExecutor::scan_factor() {
+  uniform_ = false;
+  c0_ = 0.0;
+  const std::string v = diag_value("uniform_factor");
+  RMA_CHECK_ARG(v.empty() || v == "off", "RMA_DIAG uniform_factor=" << v << " (off)");
+  // only the fast-math K-step passes have a uniform-factor kernel
+  if (v == "off" || !fast5()) return;
+  // whoever wrote 1/Cp did so on a stream of their own: wait for the device
+  RMA_HIP_CHECK(hipDeviceSynchronize());
+  uint64_t* d = nullptr;
+  RMA_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), 2 * sizeof(uint64_t)));
+  uint64_t h[2] = {1, 0};
+  try {
+    // on the executor's stream: the null stream is not ordered with it
+    RMA_HIP_CHECK(hipMemsetAsync(d, 0, 2 * sizeof(uint64_t), S(s_lo_)));
+    count_differing_gpu(iCp_, nx_ * ny_, d, s_lo_);
+    RMA_HIP_CHECK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, S(s_lo_)));
+    RMA_HIP_CHECK(hipStreamSynchronize(S(s_lo_)));
+  } catch (...) {
+    (void)hipStreamSynchronize(S(s_lo_));
+    (void)hipFree(d);
+    throw;
+  }
+  RMA_HIP_CHECK(hipFree(d));
+  if (h[0] != 0) return;
+  uniform_ = true;
+  std::memcpy(&c0_, &h[1], sizeof c0_);
+}
+
+bool DiffusionExecutor::rescan_factor() {
+  RMA_HIP_CHECK(hipStreamSynchronize(S(s_hi_)));
+  RMA_HIP_CHECK(hipStreamSynchronize(S(s_lo_)));
+  const bool was = uniform_;
+  const double c0 = c0_;
+  scan_factor();
+  if ((was != uniform_ || std::memcmp(&c0, &c0_, sizeof c0) != 0) && graph_exec_) {
+    // the captured launches hold the old kernels and arguments
+    (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(graph_exec_));
+    graph_exec_ = nullptr;
+  }
+  return uniform_;
 }
 
 bool DiffusionExecutor::fast5() const {
@@ -456,10 +501,21 @@ void DiffusionExecutor::enqueue_step(double* Tin, double* Tout) {
 void DiffusionExecutor::multi_step(int K, double* Tin, double* Tout, const double* iCp,
                                    int64_t nx, int64_t ny, const Rect* rects, int n,
                                    const StencilTuning& tn, void* stream) const {
-  if (K == 2 && tn.kernel < 5)  // dedicated two-step kernel: faster at K=2
+  if (K == 2 && tn.kernel < 5) {  // dedicated two-step kernel: faster at K=2
     stencil2_rects_gpu(Tout, Tin, iCp, nx, ny, rects, n, p_.coef, tn, stream);
-  else
+    return;
+  }
+  if (!uniform_) {
     stencilk_rects_gpu(K, Tout, Tin, iCp, nx, ny, rects, n, p_.coef, tn, stream);
+    return;
+  }
+  // uniform 1/Cp: every launch whose kernel has the variant runs it (the
+  // launcher keeps the field path for the others); prime()'s scratch field
+  // launches the same kernels (the variant does not read the array)
+  StencilTuning tu = tn;
+  tu.uniform = true;
+  tu.uniform_value = c0_;
+  stencilk_rects_gpu(K, Tout, Tin, iCp, nx, ny, rects, n, p_.coef, tu, stream);
 }
 
 bool DiffusionExecutor::fused_pass_ok(const PassGeom& g, const StencilTuning& tn) const {

@@ -194,6 +194,7 @@ class Diffusion2D:
         self._timing = False
         self._ptimes: list = []
         self.executor = None
+        self._iCp_scanned = -1
         self.use_graph = False
         use_native = cfg.executor == "native" or (
             cfg.executor == "auto" and dev.type == "cuda" and g.halo is not None)
@@ -279,6 +280,7 @@ class Diffusion2D:
             from .._native import load_lab
 
             load_lab()
+        self._iCp_scanned = self.iCp._version  # the constructor examines 1/Cp (step())
         return native().Executor(
             self.T.data_ptr(), self.T2.data_ptr() if self.T2 is not None else 0,
             self.iCp.data_ptr(), nx, ny, _MODE[cfg.variant], tuple(self.coef),
@@ -477,6 +479,11 @@ class Diffusion2D:
         if n <= 0:
             return
         if self.executor is not None:
+            # the executor examined 1/Cp when it was built (uniform-factor passes do not
+            # read the array): an in-place edit since then must be seen before it runs
+            if self.iCp._version != self._iCp_scanned:
+                self.executor.rescan_factor()
+                self._iCp_scanned = self.iCp._version
             self.executor.run(int(n), torch.cuda.current_stream(self.device).cuda_stream)
             self.parity = self.executor.parity
             self.steps_done += n

@@ -115,6 +115,11 @@ class StencilTuning:
     xcd_remap: int = -1  # -1: chosen by tile width (see csrc/kernels/stencil.hip)
     stages: int = 0  # pipe / pipec: waves per strip (0: native pipe_default_stages)
     cols: int = 0  # pipe: column waves per stage (0: native pipe_default_cols; 2 needs vec=4)
+    # piper / piper_nosb: the caller vouches that 1/Cp is bit-for-bit one value; the
+    # kernel's uniform-factor variant takes iCp[0, 0] as an argument and does not read
+    # the array (the executor decides this by scanning the array, ``uniform_factor``)
+    uniform: bool = False
+    uniform_value: float | None = None  # None: read iCp[0, 0] (synchronises the device)
 
 
 @dataclass
@@ -303,7 +308,9 @@ def stencilk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor,
         native().stencilk_rects(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, rects, tuple(coef),
                                 tn.chunk_rows, int(tn.nontemporal), stream_handle(T), True,
                                 tn.xcd_remap, tn.vec, kernel_id(tn.kernel), int(tn.stages),
-                                int(tn.cols))
+                                int(tn.cols), bool(tn.uniform),
+                                0.0 if not tn.uniform else float(iCp[0, 0])
+                                if tn.uniform_value is None else float(tn.uniform_value))
     elif _use_native_cpu():
         native().stencilk_rects(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, rects, tuple(coef),
                                 16, 0, 0, False, -1, 2, kernel_id(tn.kernel), 0)
