@@ -1,0 +1,157 @@
+#!/usr/bin/env python
+"""Sweep of the 3D z-march kernel (csrc/kernels/stencil3d.hip) on one GPU.
+
+For every cube size the tunings (rows x unroll x vec x chunk_z), the same-box
+roofline probes (stream_triad: 2 reads + 1 write, the stencil's mix; stream_copy)
+and nothing else run in interleaved rounds on alternating buffers; the report
+is the median over the rounds. T_eff = 3 * nx*ny*nz * 8 B / t. ``--ap N`` also
+times Diffusion3D's ``perf`` and ``ap`` variants at N^3 (the kernel against the
+torch expressions a user had before). ``--one`` runs a few launches of the
+default tuning and of the probes only (for a counter-collection run).
+
+    python bench/stencil3d_sweep.py --sizes 512,1024,1536 --ap 1024 --out sweep3d.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from rocm_mpi_amd import ops  # noqa: E402
+from rocm_mpi_amd._native import native  # noqa: E402
+
+
+def sweep_size(n: int, a) -> dict:
+    nat = native()
+    dev = torch.device("cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    bufs = [torch.empty((n, n, n), dtype=torch.float64, device=dev) for _ in range(2)]
+    iCp = torch.empty((n, n, n), dtype=torch.float64, device=dev)
+    geom = ops.TileGeometry3(0, 0, 0, n, n, n, 10.0 / n, 10.0 / n, 10.0 / n)
+    ops.init_random3d_(bufs[0], geom, seed=1)
+    bufs[1].copy_(bufs[0])
+    ops.init_random3d_(iCp, geom, seed=2, lo=0.5, hi=2.0)
+    d = 10.0 / n
+    coef = ops.StencilCoef3.from_physics(1.0, d, d, d, d * d / 6.1)
+    cells = float(n) ** 3
+    flip = [0]
+
+    def pair():
+        flip[0] ^= 1
+        return bufs[flip[0]], bufs[flip[0] ^ 1]
+
+    variants = {}
+    if a.one:
+        tunings = [ops.Stencil3DTuning()]
+    else:
+        tunings = [ops.Stencil3DTuning(rows=r, unroll=u, vec=v, chunk_z=cz)
+                   for r, u in ops.TUNINGS_3D for v in (2, 1) for cz in a.chunk_z
+                   if v == 2 or (r, u, cz) == (4, 2, 0)]
+        tunings += [ops.Stencil3DTuning(nontemporal=0), ops.Stencil3DTuning(xcd_remap=0)]
+    for tn in tunings:
+        name = (f"march_r{tn.rows}_u{tn.unroll}_v{tn.vec}_cz{tn.chunk_z}_nt{tn.nontemporal}"
+                f"_x{tn.xcd_remap}")
+
+        def run(tn=tn):
+            dst, src = pair()
+            ops.stencil3d_step(dst, src, iCp, coef, tuning=tn)
+
+        variants[name] = (run, 24.0 * cells)
+
+    def triad():
+        dst, src = pair()
+        nat.stream_triad(dst.data_ptr(), src.data_ptr(), iCp.data_ptr(), 0.5, int(cells), s, 1, 0)
+
+    def copy():
+        dst, src = pair()
+        nat.stream_copy(dst.data_ptr(), src.data_ptr(), int(cells), s, 1, 0)
+
+    variants["roof_triad"] = (triad, 24.0 * cells)
+    variants["roof_copy"] = (copy, 16.0 * cells)
+    times = {k: [] for k in variants}
+    for fn, _ in variants.values():  # warm every shape and code object
+        fn()
+    torch.cuda.synchronize()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.rounds):
+        for k, (fn, _) in variants.items():
+            ev0.record()
+            for _ in range(a.iters):
+                fn()
+            ev1.record()
+            ev1.synchronize()
+            times[k].append(ev0.elapsed_time(ev1) / a.iters)
+    res = {}
+    for k, (_, b) in variants.items():
+        med = statistics.median(times[k])
+        res[k] = {"median_ms": med, "min_ms": min(times[k]), "max_ms": max(times[k]),
+                  "GBps": b / med / 1e6, "T_eff_GBps": 24.0 * cells / med / 1e6}
+    tri, cp = res["roof_triad"]["median_ms"], res["roof_copy"]["GBps"]
+    for k, r in res.items():
+        if k.startswith("march"):
+            r["vs_triad"] = tri / r["median_ms"]
+            r["vs_copy_rate"] = r["GBps"] / cp
+    del bufs, iCp
+    torch.cuda.empty_cache()
+    return res
+
+
+def model_compare(n: int, steps: int) -> dict:
+    """Seconds per step of Diffusion3D perf (the kernel) and ap (torch) at n^3."""
+    from rocm_mpi_amd.models import Diffusion3D, Diffusion3DConfig
+
+    out = {}
+    for variant in ("perf", "ap", "perf", "ap"):  # alternating: two timings each
+        m = Diffusion3D(Diffusion3DConfig(variant=variant, nx=n, ny=n, nz=n, nt=steps + 2,
+                                          init="random", quiet=True))
+        res = m.run(steps + 2, warmup=2)
+        out.setdefault(variant, []).append(res.t_it * 1e3)
+        m.close()
+        del m
+        torch.cuda.empty_cache()
+    return {"n": n, "steps": steps, "perf_ms_per_step": out["perf"], "ap_ms_per_step": out["ap"],
+            "speedup": min(out["ap"]) / max(out["perf"])}
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--sizes", default="512,1024,1536")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--chunk-z", dest="chunk_z", default="0,32,128",
+                    type=lambda v: [int(x) for x in v.split(",")])
+    ap.add_argument("--ap", type=int, default=0, help="cube size of the perf-versus-ap timing")
+    ap.add_argument("--ap-steps", type=int, default=5)
+    ap.add_argument("--one", action="store_true", help="default tuning and probes only")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("stencil3d_sweep needs a GPU")
+    report = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters": a.iters,
+              "sizes": {}}
+    for n in [int(v) for v in a.sizes.split(",") if v]:
+        report["sizes"][str(n)] = sweep_size(n, a)
+        best = sorted((r["median_ms"], k) for k, r in report["sizes"][str(n)].items())
+        for ms, k in best:
+            r = report["sizes"][str(n)][k]
+            print(f"{n:5d}^3 {k:40s} {ms:9.3f} ms  {r['GBps']:8.1f} GB/s"
+                  + (f"  {r['vs_triad']:.3f} of triad" if "vs_triad" in r else ""), flush=True)
+    if a.ap:
+        report["perf_vs_ap"] = model_compare(a.ap, a.ap_steps)
+        print("perf_vs_ap", json.dumps(report["perf_vs_ap"]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(report, f, indent=1)
+    print(json.dumps({"ok": True, "sizes": list(report["sizes"])}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -56,6 +56,28 @@ TileGeom to_geom(const Geom& g) {
 }
 Rect4 from_rect(const Rect& r) { return {r.x0, r.x1, r.y0, r.y1}; }
 
+using Box6 = std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>;
+using Coef5 = std::tuple<double, double, double, double, double>;  // mlam, rdx, rdy, rdz, dt
+using Geom3 = std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, double,
+                         double, double, double, double, int, int,
+                         int>;  // g{x,y,z}0 n{x,y,z}g d{x,y,z} {x,y,z}off period{x,y,z}
+std::vector<Box> to_boxes(const std::vector<Box6>& v) {
+  std::vector<Box> b;
+  for (auto& t : v)
+    b.push_back({std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t), std::get<4>(t),
+                 std::get<5>(t)});
+  return b;
+}
+StencilCoef3 to_coef3(const Coef5& c) {
+  return {std::get<0>(c), std::get<1>(c), std::get<2>(c), std::get<3>(c), std::get<4>(c)};
+}
+TileGeom3 to_geom3(const Geom3& g) {
+  TileGeom3 t;
+  std::tie(t.gx0, t.gy0, t.gz0, t.nxg, t.nyg, t.nzg, t.dx, t.dy, t.dz, t.xoff, t.yoff, t.zoff,
+           t.periodx, t.periody, t.periodz) = g;
+  return t;
+}
+
 using FieldT = std::tuple<uintptr_t, std::array<int64_t, 3>, int, std::array<int64_t, 3>,
                           std::array<int64_t, 3>>;
 std::vector<HaloField> to_fields(const std::vector<FieldT>& v) {
@@ -186,6 +208,47 @@ PYBIND11_MODULE(_C, m) {
       py::arg("stream") = 0, py::arg("gpu") = true, py::arg("xcd_remap") = -1,
       py::arg("vec") = 2, py::arg("kernel") = 0, py::arg("stages") = 0, py::arg("cols") = 0,
       py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
+  m.def(
+      "stencil3d_boxes",
+      [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
+         const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
+         int nontemporal, int chunk_z, int xcd_remap, uintptr_t stream, bool gpu) {
+        auto b = to_boxes(boxes);
+        if (gpu) {
+          Stencil3DTuning tn;
+          tn.rows = rows;
+          tn.unroll = unroll;
+          tn.vec = vec;
+          tn.nontemporal = nontemporal;
+          tn.chunk_z = chunk_z;
+          tn.xcd_remap = xcd_remap;
+          stencil3d_boxes_gpu(P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny, nz,
+                              b.data(), (int)b.size(), to_coef3(coef), tn, S(stream));
+        } else {
+          py::gil_scoped_release nogil;
+          stencil3d_boxes_cpu(P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny, nz,
+                              b.data(), (int)b.size(), to_coef3(coef));
+        }
+      },
+      py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
+      py::arg("boxes"), py::arg("coef"), py::arg("rows") = 4, py::arg("unroll") = 2,
+      py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
+      py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true);
+  m.def("stencil3d_has", &stencil3d_has, py::arg("rows"), py::arg("unroll"));
+  m.def("init_gaussian3d", [](uintptr_t T, int64_t nx, int64_t ny, int64_t nz, const Geom3& g,
+                              double lx, double ly, double lz, uintptr_t stream, bool gpu) {
+    if (gpu)
+      init_gaussian3d_gpu(P<double>(T), nx, ny, nz, to_geom3(g), lx, ly, lz, S(stream));
+    else
+      init_gaussian3d_cpu(P<double>(T), nx, ny, nz, to_geom3(g), lx, ly, lz);
+  });
+  m.def("init_random3d", [](uintptr_t A, int64_t nx, int64_t ny, int64_t nz, const Geom3& g,
+                            uint64_t seed, double lo, double hi, uintptr_t stream, bool gpu) {
+    if (gpu)
+      init_random3d_gpu(P<double>(A), nx, ny, nz, to_geom3(g), seed, lo, hi, S(stream));
+    else
+      init_random3d_cpu(P<double>(A), nx, ny, nz, to_geom3(g), seed, lo, hi);
+  });
   m.def(
       "stream_copy",
       [](uintptr_t b, uintptr_t a, int64_t n, uintptr_t s, int nt, int blocks) {

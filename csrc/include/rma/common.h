@@ -60,4 +60,24 @@ struct StencilCoef {
   double dt;
 };
 
+// Half-open box of cells [x0,x1) x [y0,y1) x [z0,z1) of a (nz, ny, nx) field.
+struct Box {
+  int64_t x0, x1, y0, y1, z0, z1;
+  bool empty() const { return x1 <= x0 || y1 <= y0 || z1 <= z0; }
+};
+
+// Coefficients of the explicit-Euler 7-point diffusion update: the 2D
+// expression with the z flux difference subtracted last,
+//   qzF = (mlam*(T[z+1][y][x]-c))*rdz       qzB = (mlam*(c-T[z-1][y][x]))*rdz
+//   T2  = c + dt*( iCp*( ((-(qxR-qxL))*rdx - (qyU-qyD)*rdy) - (qzF-qzB)*rdz ) )
+// (qx*, qy* as in StencilCoef, c = T[z][y][x]); identical, bitwise, in the GPU
+// kernel, its CPU twin, the torch twin and the NumPy golden model.
+struct StencilCoef3 {
+  double mlam;  // -lam
+  double rdx;   // 1/dx
+  double rdy;   // 1/dy
+  double rdz;   // 1/dz
+  double dt;
+};
+
 }  // namespace rma

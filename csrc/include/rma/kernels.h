@@ -160,6 +160,37 @@ void stencilk5_rects_cpu(int K, double* T2, const double* T, const double* iCp, 
 void count_differing_gpu(const double* A, int64_t n, uint64_t* out2, stream_t stream);
 int64_t count_differing_cpu(const double* A, int64_t n);
 
+// ---------------------------------------------------------------------------
+// Fused 7-point stencil on (nz, ny, nx) fields (stencil3d.hip): one explicit
+// 3D diffusion step, T2[b] = f(T, iCp)[b] for every cell of up to kMaxBoxes
+// half-open boxes inside the interior, in ONE launch (StencilCoef3 in
+// rma/common.h has the expression). Throws before any work unless nx, ny,
+// nz >= 3, T2 != T and every non-empty box lies in [1, n-1) per dimension.
+// ---------------------------------------------------------------------------
+constexpr int kMaxBoxes = 8;
+
+struct Stencil3DTuning {
+  int rows = 4;         // R: rows of the y-band one wave keeps in registers (2, 4, 8)
+  int unroll = 2;       // planes per z-march iteration whose loads are issued together
+                        // (1 or 2; 1 only with rows = 8)
+  int vec = 2;          // cells per lane: 2 = one 16-byte access per row, 1 = scalar (also
+                        // taken for odd nx or a base that is not 16-byte aligned)
+  int nontemporal = 3;  // bit 0: NT T2 stores; bit 1: NT 1/Cp loads
+  int chunk_z = 0;      // planes one wave marches (0: 32, the measured default)
+  int xcd_remap = 1;    // 1: each XCD takes a contiguous 1/8 of the blocks
+};
+// is (rows, unroll) an instantiated march?
+bool stencil3d_has(int rows, int unroll);
+
+void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                         int64_t nz, const Box* boxes, int nboxes, const StencilCoef3& c,
+                         const Stencil3DTuning& tune, stream_t stream);
+void stencil3d_boxes_cpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                         int64_t nz, const Box* boxes, int nboxes, const StencilCoef3& c);
+// the argument checks both twins run before any work
+void validate_boxes(const double* T2, const double* T, int64_t nx, int64_t ny, int64_t nz,
+                    const Box* boxes, int nboxes);
+
 // Width (in cells) of one wave's x-strip in the march kernel; perf_hide rounds
 // its x-frame so the interior rect starts on a strip boundary.
 int stencil_vec(int64_t nx, const StencilTuning& tune);
@@ -213,6 +244,25 @@ void init_random_gpu(double* A, int64_t nx, int64_t ny, const TileGeom& g, uint6
 void init_random_cpu(double* A, int64_t nx, int64_t ny, const TileGeom& g, uint64_t seed,
                      double lo, double hi);
 void fill_gpu(double* A, int64_t n, double value, stream_t stream);
+
+// The same for a (nz, ny, nx) tile of a 3D global grid.
+struct TileGeom3 {
+  int64_t gx0, gy0, gz0;
+  int64_t nxg, nyg, nzg;
+  double dx, dy, dz;
+  double xoff, yoff, zoff;
+  int periodx, periody, periodz;
+};
+// T = exp(-(a*a) - (b*b) - (c*c)), a, b as in 2D, c = (z + dz/2) - lz/2
+void init_gaussian3d_gpu(double* T, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                         double lx, double ly, double lz, stream_t stream);
+void init_gaussian3d_cpu(double* T, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                         double lx, double ly, double lz);
+// uniform01(seed, (gz*nyg + gy)*nxg + gx) over the wrapped global indices
+void init_random3d_gpu(double* A, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                       uint64_t seed, double lo, double hi, stream_t stream);
+void init_random3d_cpu(double* A, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                       uint64_t seed, double lo, double hi);
 
 // ---------------------------------------------------------------------------
 // Halo pack / unpack (K7/K8): strided 2D block copy. Both sides have a

@@ -68,6 +68,51 @@ void stencilk_rects_cpu(int K, double* T2, const double* T, const double* iCp, i
   stencil_rects_cpu(T2, a.data(), iCp, nx, ny, rects, nrects, c);
 }
 
+void validate_boxes(const double* T2, const double* T, int64_t nx, int64_t ny, int64_t nz,
+                    const Box* boxes, int nboxes) {
+  RMA_CHECK_ARG(nboxes >= 0 && nboxes <= kMaxBoxes,
+                "nboxes=" << nboxes << " (at most " << kMaxBoxes << " boxes per launch)");
+  RMA_CHECK_ARG(nx >= 3 && ny >= 3 && nz >= 3,
+                "grid too small: nx=" << nx << " ny=" << ny << " nz=" << nz);
+  RMA_CHECK_ARG(T2 != T, "the 3D update cannot run in place (T2 aliases T)");
+  for (int i = 0; i < nboxes; ++i) {
+    const Box& b = boxes[i];
+    if (b.empty()) continue;
+    RMA_CHECK_ARG(b.x0 >= 1 && b.x1 <= nx - 1 && b.y0 >= 1 && b.y1 <= ny - 1 && b.z0 >= 1 &&
+                      b.z1 <= nz - 1,
+                  "box " << i << " [" << b.x0 << "," << b.x1 << ")x[" << b.y0 << "," << b.y1
+                         << ")x[" << b.z0 << "," << b.z1 << ") outside the interior of " << nx
+                         << "x" << ny << "x" << nz);
+  }
+}
+
+// CPU twin of stencil3d_boxes_gpu (stencil3d.hip): StencilCoef3's expression
+void stencil3d_boxes_cpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                         int64_t nz, const Box* boxes, int nboxes, const StencilCoef3& k) {
+  validate_boxes(T2, T, nx, ny, nz, boxes, nboxes);
+  const int64_t plane = nx * ny;
+  for (int i = 0; i < nboxes; ++i) {
+    const Box b = boxes[i];
+    if (b.empty()) continue;
+    const int64_t rows = b.y1 - b.y0;
+    parallel_for(0, rows * (b.z1 - b.z0), 64, [&](int64_t j) {
+      const int64_t o = (b.z0 + j / rows) * plane + (b.y0 + j % rows) * nx;
+      const double* cu = T + o;
+      for (int64_t x = b.x0; x < b.x1; ++x) {
+        const double c = cu[x];
+        const double qxR = (k.mlam * (cu[x + 1] - c)) * k.rdx;
+        const double qxL = (k.mlam * (c - cu[x - 1])) * k.rdx;
+        const double qyU = (k.mlam * (cu[x + nx] - c)) * k.rdy;
+        const double qyD = (k.mlam * (c - cu[x - nx])) * k.rdy;
+        const double qzF = (k.mlam * (cu[x + plane] - c)) * k.rdz;
+        const double qzB = (k.mlam * (c - cu[x - plane])) * k.rdz;
+        T2[o + x] = c + k.dt * (iCp[o + x] * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) -
+                                              (qzF - qzB) * k.rdz));
+      }
+    });
+  }
+}
+
 bool fast5_ok(const StencilCoef& c) {
   const double ax = (-c.mlam) * c.rdx * c.rdx, ay = (-c.mlam) * c.rdy * c.rdy;
   return ax != 0.0 && std::isfinite(ax) && std::isfinite(ay) && std::isfinite(ay / ax) &&

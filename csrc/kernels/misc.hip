@@ -81,6 +81,38 @@ __global__ void init_random_kernel(double* __restrict__ A, int64_t nx, int64_t n
   }
 }
 
+__global__ void init_gaussian3d_kernel(double* __restrict__ T, int64_t nx, int64_t ny, int64_t nz,
+                                       TileGeom3 g, double lx, double ly, double lz) {
+  const int64_t n = nx * ny * nz;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t iz = i / (nx * ny), j = i - iz * (nx * ny);
+    const int64_t iy = j / nx, ix = j - iy * nx;
+    const double x = global_coord(g.gx0 + ix, g.dx, g.xoff, g.nxg, g.periodx);
+    const double y = global_coord(g.gy0 + iy, g.dy, g.yoff, g.nyg, g.periody);
+    const double z = global_coord(g.gz0 + iz, g.dz, g.zoff, g.nzg, g.periodz);
+    const double a = (x + g.dx / 2) - lx / 2;
+    const double b = (y + g.dy / 2) - ly / 2;
+    const double c = (z + g.dz / 2) - lz / 2;
+    T[i] = exp(-(a * a) - (b * b) - (c * c));
+  }
+}
+
+__global__ void init_random3d_kernel(double* __restrict__ A, int64_t nx, int64_t ny, int64_t nz,
+                                     TileGeom3 g, uint64_t seed, double lo, double hi) {
+  const int64_t n = nx * ny * nz;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t iz = i / (nx * ny), j = i - iz * (nx * ny);
+    const int64_t iy = j / nx, ix = j - iy * nx;
+    const int64_t gx = wrap_index(g.gx0 + ix, g.nxg, g.periodx);
+    const int64_t gy = wrap_index(g.gy0 + iy, g.nyg, g.periody);
+    const int64_t gz = wrap_index(g.gz0 + iz, g.nzg, g.periodz);
+    const double u = uniform01(seed, (uint64_t)((gz * g.nyg + gy) * g.nxg + gx));
+    A[i] = lo + (hi - lo) * u;
+  }
+}
+
 __global__ void fill_kernel(double* __restrict__ A, int64_t n, double v) {
   const int64_t n2 = n / 2;
   double2* A2 = reinterpret_cast<double2*>(A);
@@ -401,6 +433,22 @@ void init_random_gpu(double* A, int64_t nx, int64_t ny, const TileGeom& g, uint6
   RMA_HIP_LAUNCH_CHECK();
 }
 
+void init_gaussian3d_gpu(double* T, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                         double lx, double ly, double lz, stream_t stream) {
+  RMA_CHECK_ARG(nx > 0 && ny > 0 && nz > 0, "empty tile");
+  init_gaussian3d_kernel<<<grid_stride_blocks(nx * ny * nz, 256), 256, 0, as_stream(stream)>>>(
+      T, nx, ny, nz, g, lx, ly, lz);
+  RMA_HIP_LAUNCH_CHECK();
+}
+
+void init_random3d_gpu(double* A, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                       uint64_t seed, double lo, double hi, stream_t stream) {
+  RMA_CHECK_ARG(nx > 0 && ny > 0 && nz > 0, "empty tile");
+  init_random3d_kernel<<<grid_stride_blocks(nx * ny * nz, 256), 256, 0, as_stream(stream)>>>(
+      A, nx, ny, nz, g, seed, lo, hi);
+  RMA_HIP_LAUNCH_CHECK();
+}
+
 void fill_gpu(double* A, int64_t n, double value, stream_t stream) {
   if (n <= 0) return;
   if ((reinterpret_cast<uintptr_t>(A) & 15) == 0)
@@ -562,6 +610,36 @@ void init_random_cpu(double* A, int64_t nx, int64_t ny, const TileGeom& g, uint6
     for (int64_t ix = 0; ix < nx; ++ix) {
       const int64_t gx = wrap_index(g.gx0 + ix, g.nxg, g.periodx);
       A[iy * nx + ix] = lo + (hi - lo) * uniform01(seed, (uint64_t)(gy * g.nxg + gx));
+    }
+  });
+}
+
+void init_gaussian3d_cpu(double* T, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                         double lx, double ly, double lz) {
+  parallel_for(0, ny * nz, 16, [&](int64_t j) {
+    const int64_t iz = j / ny, iy = j - iz * ny;
+    const double y = global_coord(g.gy0 + iy, g.dy, g.yoff, g.nyg, g.periody);
+    const double z = global_coord(g.gz0 + iz, g.dz, g.zoff, g.nzg, g.periodz);
+    const double b = (y + g.dy / 2) - ly / 2;
+    const double c = (z + g.dz / 2) - lz / 2;
+    for (int64_t ix = 0; ix < nx; ++ix) {
+      const double x = global_coord(g.gx0 + ix, g.dx, g.xoff, g.nxg, g.periodx);
+      const double a = (x + g.dx / 2) - lx / 2;
+      T[j * nx + ix] = std::exp(-(a * a) - (b * b) - (c * c));
+    }
+  });
+}
+
+void init_random3d_cpu(double* A, int64_t nx, int64_t ny, int64_t nz, const TileGeom3& g,
+                       uint64_t seed, double lo, double hi) {
+  parallel_for(0, ny * nz, 16, [&](int64_t j) {
+    const int64_t iz = j / ny, iy = j - iz * ny;
+    const int64_t gy = wrap_index(g.gy0 + iy, g.nyg, g.periody);
+    const int64_t gz = wrap_index(g.gz0 + iz, g.nzg, g.periodz);
+    for (int64_t ix = 0; ix < nx; ++ix) {
+      const int64_t gx = wrap_index(g.gx0 + ix, g.nxg, g.periodx);
+      A[j * nx + ix] =
+          lo + (hi - lo) * uniform01(seed, (uint64_t)((gz * g.nyg + gy) * g.nxg + gx));
     }
   });
 }

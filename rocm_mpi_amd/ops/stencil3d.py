@@ -1,0 +1,198 @@
+"""Tensor-level entry points of the 3D (7-point) diffusion kernels.
+
+Fields are ``(nz, ny, nx)`` float64 tensors, contiguous, x fastest. As in
+``ops.stencil`` every op validates on the host before any launch and then
+dispatches: GPU tensors to ``csrc/kernels/stencil3d.hip`` / ``misc.hip`` on
+the current torch stream (the extension is mandatory there), CPU tensors to
+the bit-identical C++ twins, or to a pure-torch formulation with the same
+operation order when the extension is absent.
+
+The canonical per-cell update (``StencilCoef3`` in csrc/include/rma/common.h) is
+the 2D expression with the z flux difference subtracted last::
+
+    T2 = c + dt*( iCp*( ((-(qxR-qxL))*rdx - (qyU-qyD)*rdy) - (qzF-qzB)*rdz ) )
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Iterable, NamedTuple, Sequence
+
+import torch
+
+from .._native import has_native, native
+from .stencil import _ptr, check_field, stream_handle
+
+Box = tuple  # (x0, x1, y0, y1, z0, z1), half-open, 0-based cell indices
+MAX_BOXES = 8
+
+
+class StencilCoef3(NamedTuple):
+    """Coefficients of the canonical 3D update (csrc/include/rma/common.h)."""
+
+    mlam: float  # -lam
+    rdx: float  # 1/dx
+    rdy: float  # 1/dy
+    rdz: float  # 1/dz
+    dt: float
+
+    @classmethod
+    def from_physics(cls, lam: float, dx: float, dy: float, dz: float,
+                     dt: float) -> "StencilCoef3":
+        return cls(-lam, 1.0 / dx, 1.0 / dy, 1.0 / dz, dt)
+
+
+@dataclass
+class Stencil3DTuning:
+    """Knobs of the z-march kernel (defaults: profiles/diffusion3d.md): rows of
+    the y-band a wave keeps in registers (2, 4, 8), planes per march iteration
+    (1 or 2; 1 with 8 rows), cells per lane (2: 16-byte accesses, 1: scalar),
+    non-temporal bitmask (1: T2 stores, 2: 1/Cp loads), planes per wave task
+    (0: the measured default, 32) and the per-XCD block order."""
+
+    rows: int = 4
+    unroll: int = 2
+    vec: int = 2
+    nontemporal: int = 3
+    chunk_z: int = 0
+    xcd_remap: int = 1
+
+
+# every (rows, unroll) the launcher instantiates
+TUNINGS_3D = ((2, 1), (2, 2), (4, 1), (4, 2), (8, 1))
+
+
+@dataclass
+class TileGeometry3:
+    """Placement of a local (nz, ny, nx) tile in the implicit global grid."""
+
+    gx0: int
+    gy0: int
+    gz0: int
+    nxg: int
+    nyg: int
+    nzg: int
+    dx: float
+    dy: float
+    dz: float
+    xoff: float = 0.0
+    yoff: float = 0.0
+    zoff: float = 0.0
+    periodx: int = 0
+    periody: int = 0
+    periodz: int = 0
+
+    def as_tuple(self):
+        return (int(self.gx0), int(self.gy0), int(self.gz0), int(self.nxg), int(self.nyg),
+                int(self.nzg), float(self.dx), float(self.dy), float(self.dz), float(self.xoff),
+                float(self.yoff), float(self.zoff), int(self.periodx), int(self.periody),
+                int(self.periodz))
+
+
+def interior_box(nx: int, ny: int, nz: int) -> Box:
+    return (1, nx - 1, 1, ny - 1, 1, nz - 1)
+
+
+def validate_boxes(boxes: Sequence[Box], nx: int, ny: int, nz: int) -> list[Box]:
+    if len(boxes) > MAX_BOXES:
+        raise ValueError(f"at most {MAX_BOXES} boxes per launch, got {len(boxes)}")
+    out = []
+    for b in boxes:
+        x0, x1, y0, y1, z0, z1 = (int(v) for v in b)
+        if x1 <= x0 or y1 <= y0 or z1 <= z0:
+            continue
+        if x0 < 1 or y0 < 1 or z0 < 1 or x1 > nx - 1 or y1 > ny - 1 or z1 > nz - 1:
+            raise ValueError(f"box {tuple(b)} outside the interior "
+                             f"[1,{nx - 1})x[1,{ny - 1})x[1,{nz - 1})")
+        out.append((x0, x1, y0, y1, z0, z1))
+    return out
+
+
+def stencil3d_torch(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, c: StencilCoef3,
+                    boxes: Iterable[Box]) -> None:
+    """Pure-torch twin of the fused 3D kernel (same operation order, bitwise)."""
+    for x0, x1, y0, y1, z0, z1 in boxes:
+        cu = T[z0:z1, y0:y1, x0:x1]
+        qxR = (c.mlam * (T[z0:z1, y0:y1, x0 + 1:x1 + 1] - cu)) * c.rdx
+        qxL = (c.mlam * (cu - T[z0:z1, y0:y1, x0 - 1:x1 - 1])) * c.rdx
+        qyU = (c.mlam * (T[z0:z1, y0 + 1:y1 + 1, x0:x1] - cu)) * c.rdy
+        qyD = (c.mlam * (cu - T[z0:z1, y0 - 1:y1 - 1, x0:x1])) * c.rdy
+        qzF = (c.mlam * (T[z0 + 1:z1 + 1, y0:y1, x0:x1] - cu)) * c.rdz
+        qzB = (c.mlam * (cu - T[z0 - 1:z1 - 1, y0:y1, x0:x1])) * c.rdz
+        d = iCp[z0:z1, y0:y1, x0:x1] * (((-(qxR - qxL)) * c.rdx - (qyU - qyD) * c.rdy)
+                                        - (qzF - qzB) * c.rdz)
+        T2[z0:z1, y0:y1, x0:x1] = cu + c.dt * d
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: StencilCoef3,
+                   boxes: Sequence[Box] | None = None,
+                   tuning: Stencil3DTuning | None = None) -> None:
+    """One explicit 3D diffusion step on every box (default: the interior):
+    T2[b] = T[b] + dt*iCp*(div q)[b]. Cells outside the boxes keep T2's values."""
+    check_field("T", T)
+    if T.dim() != 3:
+        raise ValueError(f"T must be a (nz, ny, nx) field, got shape {tuple(T.shape)}")
+    nz, ny, nx = T.shape
+    if min(nx, ny, nz) < 3:
+        raise ValueError(f"nx, ny, nz >= 3 required, got (nz, ny, nx) = {tuple(T.shape)}")
+    check_field("T2", T2, (nz, ny, nx), T.device)
+    check_field("iCp", iCp, (nz, ny, nx), T.device)
+    if _overlap(T2, T):
+        raise ValueError("T2 must not alias T (double buffering)")
+    boxes = validate_boxes(boxes if boxes is not None else [interior_box(nx, ny, nz)],
+                           nx, ny, nz)
+    if not boxes:
+        return
+    coef = StencilCoef3(*coef)
+    if T.is_cuda:
+        tn = tuning or Stencil3DTuning()
+        native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
+                                 int(tn.rows), int(tn.unroll), int(tn.vec), int(tn.nontemporal),
+                                 int(tn.chunk_z), int(tn.xcd_remap), stream_handle(T), True)
+    elif has_native():
+        native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
+                                 4, 1, 2, 0, 0, 0, 0, False)
+    else:
+        stencil3d_torch(T2, T, iCp, coef, boxes)
+
+
+def _check3(name: str, t: torch.Tensor):
+    check_field(name, t)
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be a (nz, ny, nx) field, got shape {tuple(t.shape)}")
+    return t.shape
+
+
+def init_gaussian3d_(T: torch.Tensor, geom: TileGeometry3, lx: float, ly: float,
+                     lz: float) -> torch.Tensor:
+    """T = exp(-(x_g+dx/2-lx/2)^2 - (y_g+dy/2-ly/2)^2 - (z_g+dz/2-lz/2)^2)."""
+    nz, ny, nx = _check3("T", T)
+    if T.is_cuda or has_native():
+        native().init_gaussian3d(_ptr(T), nx, ny, nz, geom.as_tuple(), lx, ly, lz,
+                                 stream_handle(T), T.is_cuda)
+    else:
+        from ..parallel.geometry import coords_1d
+
+        x = coords_1d(geom.gx0, nx, geom.dx, geom.xoff, geom.nxg, geom.periodx)
+        y = coords_1d(geom.gy0, ny, geom.dy, geom.yoff, geom.nyg, geom.periody)
+        z = coords_1d(geom.gz0, nz, geom.dz, geom.zoff, geom.nzg, geom.periodz)
+        a = (x + geom.dx / 2) - lx / 2
+        b = (y + geom.dy / 2) - ly / 2
+        c = (z + geom.dz / 2) - lz / 2
+        T.copy_(torch.exp(-(a * a)[None, None, :] - (b * b)[None, :, None]
+                          - (c * c)[:, None, None]))
+    return T
+
+
+def init_random3d_(A: torch.Tensor, geom: TileGeometry3, seed: int = 0, lo: float = 0.0,
+                   hi: float = 1.0) -> torch.Tensor:
+    """Counter-based uniform field keyed by the global cell index
+    ``(gz*nyg + gy)*nxg + gx``: the same field for every decomposition."""
+    nz, ny, nx = _check3("A", A)
+    native().init_random3d(_ptr(A), nx, ny, nz, geom.as_tuple(), int(seed) & (2**64 - 1), lo, hi,
+                           stream_handle(A), A.is_cuda)
+    return A
