@@ -121,7 +121,9 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--K", type=int, nargs="+", default=[20, 24])
     ap.add_argument("--S", type=int, default=4)
-    ap.add_argument("--V", type=int, default=4)
+    ap.add_argument("--V", "--vec", dest="V", type=int, default=4,
+                    help="cells per lane (6: the uniform-factor kernels of K = 17..24, with "
+                         "--uniform)")
     ap.add_argument("--ar", type=int, default=-1,
                     help="arithmetic template (-1: the executor's: 13 = piper without in-level "
                          "barriers at K = 24, 3 = piper elsewhere)")

@@ -67,6 +67,10 @@ def main(argv=None):
                     help="depths timed like --exec but with the uniform-factor variant of the "
                          "kernel (1/Cp is one value here; rows kernel='exec_uni'): the A/B of "
                          "profiles/r7/uniform_factor.md")
+    ap.add_argument("--exec-uniform6", dest="exec_uni6", default="",
+                    help="depths timed like --exec-uniform but at six cells per lane (K = 17..24; "
+                         "rows kernel='exec_uni6'): the A/B of profiles/r8/six_cells.md. Rows "
+                         "per task other than the executor's: --kinds exec_uni6:K:rows")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
 
@@ -130,6 +134,7 @@ def main(argv=None):
     cfgs += [("pipe5", K, 0) for K in krange(a.pipe5)]
     cfgs += [("exec", K, 0) for K in krange(a.exec_k)]
     cfgs += [("exec_uni", K, 0) for K in krange(a.exec_uni)]
+    cfgs += [("exec_uni6", K, 0) for K in krange(a.exec_uni6)]
     for item in filter(None, a.kinds.split(",")):
         k, K, *c = item.split(":")  # kernel:K[:chunk_rows]
         cfgs.append((k, int(K), 0, int(c[0])) if c else (k, int(K), 0))
@@ -142,6 +147,7 @@ def main(argv=None):
         for c in cs.split("/"):
             cfgs.append(("pipe2", int(K), 0, int(c)))
 
+    EXEC = ("exec", "exec_uni", "exec_uni6")
     rect = [ops.interior_rect(n, n)]
     names = {v: k for k, v in {**ops.KERNELS, **ops.LAB_KERNELS}.items()}
     # every configuration at every coefficient grid: (spec, kind, K, S[, chunk])
@@ -153,10 +159,11 @@ def main(argv=None):
             ops.stencil_step(T2, T, iCp, coef, rect, ops.StencilTuning())
         elif kind == "two_step":
             ops.stencil2_step(T2, T, iCp, coef, rect, ops.StencilTuning(chunk_rows=16, unroll=2))
-        elif kind in ("exec", "exec_uni"):
+        elif kind in EXEC:
             kid, vec, ch = N.fast_kernel_k(K, n, tuple(coef))
-            tn = ops.StencilTuning(chunk_rows=ch, kernel=names[kid], vec=vec, xcd_remap=1,
-                                   uniform=kind == "exec_uni", uniform_value=1.0)
+            tn = ops.StencilTuning(chunk_rows=c or ch, kernel=names[kid],
+                                   vec=6 if kind == "exec_uni6" else vec, xcd_remap=1,
+                                   uniform=kind != "exec", uniform_value=1.0)
             ops.stencilk_step(K, T2, T, iCp, coef, rect, tn)
         else:
             vec = 2 if kind in ("lds_dpp", "fast5") else 5 if kind == "pipe5" else 4
@@ -189,15 +196,18 @@ def main(argv=None):
         cs, c = c[0], c[1:]
         kind, K, S = c[:3]
         med = statistics.median(times[(cs,) + c])
-        ek = (names[N.fast_kernel_k(K, n, tuple(coefs[cs]))[0]] if kind in ("exec", "exec_uni") else None)
+        ek = (names[N.fast_kernel_k(K, n, tuple(coefs[cs]))[0]] if kind in EXEC else None)
         rows.append({"coef_dims": cs, "ry": round(ops.fast5_constants(coefs[cs])[0], 6),
                      "kernel": kind, "exec_kernel": ek, "K": K, "stages": S or (native().pipe_default_stages(K)
                                                              if kind in ops.PIPE + ("pipe2", "pipe5")
                                                              else 0),
-                     "chunk_rows": (N.fast_kernel_k(K, n, tuple(coefs[cs]))[2] if kind in ("exec", "exec_uni")
+                     "chunk_rows": ((c[3] if len(c) > 3 else 0) or
+                                    N.fast_kernel_k(K, n, tuple(coefs[cs]))[2] if kind in EXEC
                                     else chunk(K, c[3] if len(c) > 3 else 0, kind)
                                     if kind not in ("march", "two_step") else None),
-                     "vec": (N.pipe_vec(K, S, 0, n, 5, True) if kind == "pipe5" else None),
+                     "vec": (N.pipe_vec(K, S, 0, n, 5, True) if kind == "pipe5" else
+                             N.pipe_vec_uniform(K, S, N.fast_kernel_k(K, n, tuple(coefs[cs]))[0] - 9,
+                                                n, 6, True, True) if kind == "exec_uni6" else None),
                      "ms_per_pass": round(med, 3), "ms_min": round(min(times[(cs,) + c]), 3),
                      "ms_per_step": round(med / K, 4), "rel": round(med / base, 4),
                      "teff_equiv_GBps": round(K * 24 * n * n / 1e9 / (med / 1e3), 1)})

@@ -47,12 +47,16 @@ if which == "piper":  # the executor's register-factor kernel alone (scheduler A
     # uniform-factor variant (profiles/r7/uniform_factor.md)
     kern = os.environ.get("RMA_PROBE_KERNELS", "piper").split(",")[0]
     uni = os.environ.get("RMA_PROBE_UNIFORM", "0") == "1"
+    # RMA_PROBE_VEC=6: six cells per lane (uniform variant, K = 17..24;
+    # profiles/r8/six_cells.md)
+    vec = int(os.environ.get("RMA_PROBE_VEC", "4"))
     for _ in range(reps):
         ops.stencilk_step(K, T2, T, iCp, c, rect,
-                          ops.StencilTuning(chunk_rows=ch, xcd_remap=1, kernel=kern, vec=4,
+                          ops.StencilTuning(chunk_rows=ch, xcd_remap=1, kernel=kern, vec=vec,
                                             uniform=uni, uniform_value=1.0))
     torch.cuda.synchronize()
-    print(f"probe done n={n} reps={reps} set={which} K={K} chunk={ch} kernel={kern} uniform={uni}")
+    print(f"probe done n={n} reps={reps} set={which} K={K} chunk={ch} kernel={kern} uniform={uni} "
+          f"vec={vec}")
     sys.exit(0)
 if which == "cols":  # piper with 1 vs 2 column waves per stage
     from rocm_mpi_amd._native import load_lab

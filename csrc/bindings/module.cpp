@@ -545,6 +545,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("default_chunk_k", [](int K, int64_t ny) { return default_tune_k(K, ny).chunk_rows; },
         py::arg("K"), py::arg("ny"));
   m.def("plan_passes", &plan_passes, py::arg("nsteps"), py::arg("costs"));
+  m.def("uniform_pass_costs", &uniform_pass_costs, py::arg("kmax"), py::arg("cells") = 0.0);
+  m.def("pipe_uniform_cells", &pipe_uniform_cells, py::arg("K"), py::arg("cells"));
   m.def("default_pass_costs", &default_pass_costs, py::arg("kmax"), py::arg("fast5"),
         py::arg("cells") = 0.0);
   m.def("pipe_default_stages", &pipe_default_stages, py::arg("K"));
@@ -554,6 +556,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("cols"));
   m.def("pipe_vec", &pipe_vec, py::arg("K"), py::arg("stages"), py::arg("arith"), py::arg("nx"),
         py::arg("requested"), py::arg("aligned16") = true);
+  m.def("pipe_vec_uniform", &pipe_vec_uniform, py::arg("K"), py::arg("stages"), py::arg("arith"),
+        py::arg("nx"), py::arg("requested"), py::arg("aligned16") = true,
+        py::arg("uniform") = false);
   m.def("pipe_max_k", []() { return kPipeMaxK; });
   m.def(
       "pass_geometry",
@@ -718,6 +723,7 @@ PYBIND11_MODULE(_C, m) {
             d["frame_tall"] = rl(g.frame_tall);
             d["interior"] = from_rect(g.interior);
             d["tasks"] = g.tasks();  // the interior grid's tasks (fused / one-launch policy)
+            d["task_w"] = g.task_w;  // output columns per strip of the pass's kernel
             return d;
           },
           py::arg("K"));

@@ -191,6 +191,7 @@ class DiffusionExecutor {
   void scan_factor();
   bool uniform_ = false;  // 1/Cp is the one value c0_ (scan_factor)
   double c0_ = 0.0;
+  int cells_ = 0;  // RMA_DIAG pipe_cells=4 | 6 (read with the scan; 0: by tile class)
 
   double* T_;
   double* T2_;
@@ -206,6 +207,7 @@ class DiffusionExecutor {
   std::vector<char> geom_ok_;
   std::vector<double> cost_;     // index K: relative pass cost (plan_passes)
   std::vector<double> cost_base_;  // ...without the direct-store pricing (set_direct)
+  std::vector<double> cost_uni_;   // ...of the uniform-factor passes (uniform_pass_costs)
   int64_t hwx_ = 1, hwy_ = 1;
   void* s_hi_ = nullptr;  // hipStream_t
   void* s_lo_ = nullptr;

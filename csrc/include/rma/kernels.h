@@ -53,7 +53,8 @@ struct StencilTuning {
   int nontemporal = 3;     // bit 0: NT T2 stores; bit 1: NT 1/Cp loads; bit 2: NT T loads
   int kernel = 0;          // 0 = register march (default), 1 = LDS-tiled
   int unroll = 4;          // rows per march iteration whose loads are issued together
-  int vec = 2;             // cells per lane (2: one 16-B access per row, 4: two)
+  int vec = 2;             // cells per lane (2: one 16-B access per row, 4: two; 6: three,
+                           // uniform-factor pipelined kernels only, pipe_vec_uniform)
   int xcd_remap = -1;      // 1: each XCD takes a contiguous 1/8 of the tasks; 0: chunk rows
                            // padded to 8-block multiples (same-XCD neighbours); -1: by size
   int stages = 0;          // pipelined K-step kernels 9/10: waves per strip (0: default)
@@ -135,6 +136,16 @@ int pipe_default_cols(int K, int stages, int arith);
 // aligned accesses), else 4 / 2 with 16-B aligned arrays and nx % 4 / % 2,
 // else 1. The executor's frame geometry uses the same answer.
 int pipe_vec(int K, int stages, int arith, int64_t nx, int requested, bool aligned16);
+// ... of a launch that may run the uniform-factor variant (uniform: 1/Cp is one
+// value and the launch stores no halos directly). requested = 6 then runs six
+// cells per lane (384-column windows) where the instantiation exists (piper K =
+// 17..23, piper_nosb K = 24), the arrays are 16-B aligned and nx is even (loads
+// are clamped per 16-byte pair, so nx need not be a multiple of 6); every
+// other case resolves as pipe_vec does, a request of 6 as one of 4. This is
+// what stencil_pipe_rects_gpu runs; pipe_vec callers that do not know about
+// uniformity (the benchmark's kstep_kernel report) keep answering 4.
+int pipe_vec_uniform(int K, int stages, int arith, int64_t nx, int requested, bool aligned16,
+                     bool uniform);
 // Blocks per CU of the core pipelined kernel (occ[0]) and of its direct-store
 // variant (occ[1]; 0 when it has none; both 0 outside the core library) for
 // (K, stages, arith, V): the

@@ -99,6 +99,15 @@ FrameLayout frame_layout(int64_t ny, const Neighbors& nbr);
 // cells = nx*ny of the tile (0: the 288 GB tile): the nearest measured tile
 // class (4096^2, 8192^2, 16384^2, 101376^2) in log scale.
 std::vector<double> default_pass_costs(int kmax, bool fast5, double cells = 0);
+// The fast-math row of a tile whose 1/Cp is one value (the executor's
+// uniform-factor passes, no direct-store halos): measured for the 288 GB tile
+// class only (cells >= 98304^2; K >= 10 the uniform variant, K = 17..24 at six
+// cells per lane); every other tile gets default_pass_costs(kmax, true, cells).
+std::vector<double> uniform_pass_costs(int kmax, double cells);
+// Cells per lane the executor requests for a uniform-factor pass of depth K on
+// a tile of `cells` cells: 6 where a same-run sweep showed a gain (the 288 GB
+// class, K = 17..24), else 4. Tasks per pass scale with the cell count.
+int pipe_uniform_cells(int K, double cells);
 // RMA_DIAG pass_costs=K:cost/K:cost/... overrides entries (sweeps, tests;
 // this function takes the entries comma-separated).
 void apply_cost_overrides(std::vector<double>& cost, const char* spec);

@@ -60,6 +60,15 @@ int pipe_vec(int K, int stages, int arith, int64_t nx, int requested, bool align
   return 1;
 }
 
+int pipe_vec_uniform(int K, int stages, int arith, int64_t nx, int requested, bool aligned16,
+                     bool uniform) {
+  const int S = stages > 0 ? stages : pipe_default_stages(K);
+  // the load position is clamped per 16-byte pair, so any even nx will do
+  if (requested == 6 && uniform && aligned16 && nx % 2 == 0 && pipe::pipe_has_v6(K, S, arith))
+    return 6;
+  return pipe_vec(K, stages, arith, nx, requested == 6 ? 4 : requested, aligned16);
+}
+
 int stencil_vec(int64_t nx, const StencilTuning& tune) {
   // cells per lane: 16-byte rows need an even nx; V=4 also needs nx % 4 == 0
   // (a clamped lane past the row end must still load its own cells)

@@ -24,5 +24,11 @@ inline bool pipe_has_v5(int K, int S, int ar) {
   return ar == kArFast5 && S == 4 && K >= 16 && K <= 20;
 }
 
+// 6 cells per lane: the uniform-factor variant of the register-factor kernels,
+// S = 4, K = 17..23 (piper) and K = 24 (piper_nosb), in the core units r / r20 / r24
+inline bool pipe_has_v6(int K, int S, int ar) {
+  return S == 4 && ((ar == kArFast5Reg && K >= 17 && K <= 23) || (ar == kArFast5RegNoSB && K == 24));
+}
+
 }  // namespace pipe
 }  // namespace rma

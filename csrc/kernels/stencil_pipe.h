@@ -161,6 +161,13 @@ constexpr int waves_per_simd() {
 // every level's factor is g = gs * c0 inside the interior and 0.0 outside, a
 // scalar select per level. Without factor rows nothing outlives the 3-row
 // window rotation, so the row loop unrolled by 3 has no back-edge moves.
+//
+// Six cells per lane (V = 6, Uni only, K = 17..24; profiles/r8/six_cells.md):
+// without factor rows the carried state is 2 H V doubles, which fits two waves
+// per SIMD at V = 6 (216-218 VGPRs at H = 5, 254-256 at H = 6, no scratch).
+// 384-column windows recompute 2K of 384 columns (K=24: 1.143x instead of
+// 1.231x) and move 4 lane values per 6 cells. Loads are clamped per 16-byte
+// pair, so any even nx runs it. Per pass at 101120^2: K = 24 62.4 vs 68.6 ms.
 template <int K, int S, int Ar, bool Uni = false>
 constexpr bool pipe_u6() {
   return ar_reg(Ar) && !Uni && Plan<K, S>::H == 5;
@@ -173,13 +180,13 @@ template <int K, int S, int Ar, bool Uni = false>
 constexpr int staging_rows() {
   return pipe_u6<K, S, Ar, Uni>() ? 6 : 3;
 }
-// T + factor hand-off rows (block-wide, WB columns), LDS-DMA staging (V = 2, 4;
+// T + factor hand-off rows (block-wide, WB columns), LDS-DMA staging (V = 2, 4, 6;
 // private to each column's stage-0 wave, W columns each). Uniform factor: the T
 // rows only, of both.
 template <int K, int S, int V, int Ar, int C = 1, bool Uni = false>
 constexpr int lds_bytes_reg() {
   return ((Uni ? 2 : 4) * (S > 1 ? S - 1 : 1) * Geo<K, S, V, C>::WB +
-          (V == 2 || V == 4
+          (V == 2 || V == 4 || V == 6
                ? (Uni ? 1 : 2) * staging_rows<K, S, Ar, Uni>() * Geo<K, S, V, C>::W * C
                : 0)) *
              8 +
@@ -252,8 +259,9 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   using P = Plan<K, S>;
   constexpr bool Canon = Ar == kArCanon, kRegG = ar_reg(Ar);
   static_assert(!kRegG || (V != 5 && (C == 1 || V == 4)),
-                "register factors: V <= 4; two column waves at V = 4 only");
-  // register factors, 2 or 4 cells per lane: stage 0 prefetches T / 1/Cp three
+                "register factors: V = 1, 2, 4 (6: uniform factor); two column waves at V = 4 "
+                "only");
+  // register factors, 2, 4 or 6 cells per lane: stage 0 prefetches T / 1/Cp three
   // rows ahead by LDS-DMA (global_load_lds_dwordx4 into three staging rows per
   // array) instead of two rows ahead into 4 rows of registers, which the
   // register factors need (K=24: 256 VGPRs + 6 spilled with the register
@@ -261,10 +269,14 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // 81.6 ms per pass; with LDS-DMA 234 VGPRs). The row barrier is then a raw
   // s_barrier after lgkmcnt(0): __syncthreads() would also wait vmcnt(0) and
   // drain the prefetch every row.
-  constexpr bool kGlds = kRegG && (V == 2 || V == 4);
+  constexpr bool kGlds = kRegG && (V == 2 || V == 4 || V == 6);
   static_assert(!Uni || (kGlds && C == 1 && !Dir),
-                "uniform factor: register factors, 2 or 4 cells per lane, one column wave, "
+                "uniform factor: register factors, 2, 4 or 6 cells per lane, one column wave, "
                 "no direct stores");
+  // six cells per lane (384-column windows: K=24 recomputes 1.143x instead of
+  // 1.231x, 4 lane moves per 6 cells): only without factor rows, whose 2 H V
+  // doubles of carried rows then fit beside the levels' temporaries
+  static_assert(V != 6 || Uni, "6 cells per lane: the uniform-factor variant only");
   constexpr bool kU6 = pipe_u6<K, S, Ar, Uni>();
   constexpr int NST = staging_rows<K, S, Ar, Uni>();  // staging rows per array
   using G = Geo<K, S, V, C>;
@@ -313,6 +325,16 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // byte offsets in 32 bits: uniform 64-bit row base + zero-extended 32-bit
   // offset is the SGPR-base + VGPR-offset (saddr) addressing form
   const uint32_t xob = xo * 8u, xsob = xso * 8u;
+  // 6 cells per lane: the load position clamped per 16-byte pair, so nx need
+  // not be a multiple of 6 (strip origins are: x is even, and with nx even a
+  // pair lies wholly inside the array or wholly outside, where its slots hold
+  // copies of the edge pair; the boundary columns keep g = 0 through cin[])
+  uint32_t xpb[V == 6 ? 3 : 1];
+  if constexpr (V == 6) {
+#pragma unroll
+    for (int h = 0; h < 3; ++h)
+      xpb[h] = (uint32_t)min(max(x + 2 * h, (int64_t)0), nx - 2) * 8u;
+  }
   auto at = [](const double* base, uint32_t boff) {
     return reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + boff);
   };
@@ -358,7 +380,16 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   auto rowc = [&](int y) { return (int64_t)min(max(y, 0), ny32 - 1); };
   auto rowp = [&](const double* a, int y) { return at(a + rowc(y) * nx, xob); };
   if (stage == 0) {
-    load_row<V>(w[0][2], rowp(T, i));
+    if constexpr (V == 6) {
+#pragma unroll
+      for (int h = 0; h < 3; ++h) {
+        const dbl2 t2 = *reinterpret_cast<const dbl2*>(at(T + rowc(i) * nx, xpb[h]));
+        w[0][2][2 * h] = t2.x;
+        w[0][2][2 * h + 1] = t2.y;
+      }
+    } else {
+      load_row<V>(w[0][2], rowp(T, i));
+    }
     if constexpr (!kGlds) {
       load_row<V>(pT, rowp(T, i + 1));
       load_row<V>(pC, rowp(iCp, i));
@@ -411,7 +442,8 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
     const double* rb = (a ? iCp : T) + rowc(y) * nx;
 #pragma unroll
     for (int h = 0; h < V / 2; ++h)
-      __builtin_amdgcn_global_load_lds(at(rb, xob + 16u * h), stg(a, r) + h * 2 * kWave, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(at(rb, V == 6 ? xpb[h] : xob + 16u * h),
+                                       stg(a, r) + h * 2 * kWave, 16, 0, 0);
   };
   if constexpr (kGlds) {
     if (stage == 0) {  // rows i+1..i+NST of T and i..i+NST-1 of 1/Cp, in the order they are waited for
@@ -443,7 +475,7 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
       }
     }
   };
-  auto rds = [&](const double* row, double (&out)[V]) {  // a staging row (V = 2, 4)
+  auto rds = [&](const double* row, double (&out)[V]) {  // a staging row (V = 2, 4, 6)
 #pragma unroll
     for (int h = 0; h < V / 2; ++h) {
       const dbl2 t2 = reinterpret_cast<const dbl2*>(row)[h * kWave + lane];
@@ -609,6 +641,18 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
           const double gu = __hiloint2double(rin ? gUhi : 0, rin ? gUlo : 0);
 #pragma unroll
           for (int v = 0; v < V; ++v) gl[v] = gu;
+        } else if constexpr (V == 6) {
+          // the row test opaque per level: level j+1 tests next iteration the
+          // row level j tests now, and the unrolled loop would otherwise keep
+          // each row's V selected factors in registers for the levels to come
+          // (+12 VGPRs per level in flight: 40-290 spilled at K = 17..24)
+          int rz = __builtin_amdgcn_readfirstlane((int)rin);
+          asm volatile("" : "+s"(rz));
+          // (and the factor selected from the scalar pair by the column masks:
+          // no gc[] rows in registers)
+          const double gu = __hiloint2double(rz ? gUhi : 0, rz ? gUlo : 0);
+#pragma unroll
+          for (int v = 0; v < V; ++v) gl[v] = cin[v] ? gu : 0.0;
         } else {
 #pragma unroll
           for (int v = 0; v < V; ++v) gl[v] = rin ? gc[v] : 0.0;
@@ -786,11 +830,12 @@ constexpr bool has_direct() {
   return C == 1 && V != 5 && (Ar == kArFast5 || Ar == kArFast5Reg || Ar == kArFast5RegNoSB);
 }
 
-// uniform-factor variants: the register-factor arithmetics at 2 or 4 cells per
-// lane, one column wave, in the units that ask for them (RMA_PIPE_CASE_U)
+// uniform-factor variants: the register-factor arithmetics at 2, 4 or 6 cells
+// per lane, one column wave, in the units that ask for them (RMA_PIPE_CASE_U,
+// RMA_PIPE_CASE_U6)
 template <int V, int Ar, int C>
 constexpr bool has_uniform() {
-  return C == 1 && (V == 2 || V == 4) && (Ar == kArFast5Reg || Ar == kArFast5RegNoSB);
+  return C == 1 && (V == 2 || V == 4 || V == 6) && (Ar == kArFast5Reg || Ar == kArFast5RegNoSB);
 }
 
 struct PipeLaunch {
@@ -820,11 +865,16 @@ void launch(const PipeLaunch& a) {
   if (a.occupancy) {
     const int bs = kWave * S * C;
     a.occupancy[0] = a.occupancy[1] = 0;
-    RMA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &a.occupancy[0], pipe_kernel<K, S, V, Ar, C, false>, bs, 0));
-    if constexpr (has_direct<V, Ar, C>())
+    if constexpr (V == 6) {  // the uniform-factor kernel is the only one at six cells
       RMA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &a.occupancy[1], pipe_kernel<K, S, V, Ar, C, true>, bs, 0));
+          &a.occupancy[0], pipe_kernel<K, S, V, Ar, C, false, true>, bs, 0));
+    } else {
+      RMA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &a.occupancy[0], pipe_kernel<K, S, V, Ar, C, false>, bs, 0));
+      if constexpr (has_direct<V, Ar, C>())
+        RMA_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &a.occupancy[1], pipe_kernel<K, S, V, Ar, C, true>, bs, 0));
+    }
     return;
   }
   int rows_buf[kMaxRects] = {};
@@ -847,25 +897,36 @@ void launch(const PipeLaunch& a) {
     L.sig_blocks = L.block_end[ns - 1];
   }
   const dim3 grid((unsigned)blocks), block(kWave * S * C);
-  if (a.direct && a.direct->on) {
-    if constexpr (has_direct<V, Ar, C>()) {
-      pipe_kernel<K, S, V, Ar, C, true><<<grid, block, 0, a.stream>>>(
-          a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, *a.direct, 0.0);
-    } else {
-      RMA_CHECK_ARG(false, "no direct-store variant of the pipelined kernel K=" << K << " S=" << S
-                                << " V=" << V << " arithmetic " << Ar << " columns " << C);
-    }
-    return;
-  }
-  if constexpr (WithUni && has_uniform<V, Ar, C>()) {
-    if (a.uniform) {
-      pipe_kernel<K, S, V, Ar, C, false, true><<<grid, block, 0, a.stream>>>(
-          a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, a.c0);
+  if constexpr (V == 6) {
+    // six cells per lane: the uniform-factor kernel only (pipe_vec_uniform
+    // resolves to 6 for uniform launches without direct stores, nothing else)
+    static_assert(WithUni && has_uniform<V, Ar, C>(), "6 cells per lane: uniform factor");
+    RMA_CHECK_ARG(a.uniform && !(a.direct && a.direct->on),
+                  "6 cells per lane without a uniform 1/Cp or with direct-store halos");
+    pipe_kernel<K, S, V, Ar, C, false, true><<<grid, block, 0, a.stream>>>(
+        a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, a.c0);
+  } else {
+    if (a.direct && a.direct->on) {
+      if constexpr (has_direct<V, Ar, C>()) {
+        pipe_kernel<K, S, V, Ar, C, true><<<grid, block, 0, a.stream>>>(
+            a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, *a.direct, 0.0);
+      } else {
+        RMA_CHECK_ARG(false, "no direct-store variant of the pipelined kernel K="
+                                 << K << " S=" << S << " V=" << V << " arithmetic " << Ar
+                                 << " columns " << C);
+      }
       return;
     }
+    if constexpr (WithUni && has_uniform<V, Ar, C>()) {
+      if (a.uniform) {
+        pipe_kernel<K, S, V, Ar, C, false, true><<<grid, block, 0, a.stream>>>(
+            a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, a.c0);
+        return;
+      }
+    }
+    pipe_kernel<K, S, V, Ar, C><<<grid, block, 0, a.stream>>>(
+        a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, 0.0);
   }
-  pipe_kernel<K, S, V, Ar, C><<<grid, block, 0, a.stream>>>(
-      a.T2, a.T, a.iCp, a.nx, a.ny, L, a.k, a.chunk_rows, a.remap, DirectStores{}, 0.0);
 }
 
 // Each stencil_pipe_{a,b,c}.hip unit instantiates a range of (K, S) of the
@@ -903,3 +964,11 @@ bool dispatch_r24(int K, int S, int V, int ar, const PipeLaunch& a);
     else launch<KK, SS, 1, CC>(a);                                 \
     return true;                                                   \
   }
+
+// ... and the six-cell uniform-factor kernel (pipe_has_v6)
+#define RMA_PIPE_CASE_U6(KK, SS, CC)                               \
+  if (K == KK && S == SS && ar == CC && V == 6) {                  \
+    launch<KK, SS, 6, CC, 1, true>(a);                             \
+    return true;                                                   \
+  }                                                                \
+  RMA_PIPE_CASE_U(KK, SS, CC)

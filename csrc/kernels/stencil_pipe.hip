@@ -60,7 +60,9 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
   const bool aligned = ((reinterpret_cast<uintptr_t>(T) & 15) == 0) &&
                        ((reinterpret_cast<uintptr_t>(T2) & 15) == 0) &&
                        ((reinterpret_cast<uintptr_t>(iCp) & 15) == 0);
-  const int V = pipe_vec(K, S, arith, nx, tune.vec, aligned);
+  // (six cells per lane: the uniform-factor variant only, which has no direct stores)
+  const bool uni = tune.uniform && !(tune.direct && tune.direct->on);
+  const int V = pipe_vec_uniform(K, S, arith, nx, tune.vec, aligned, uni);
   int C = tune.cols > 0 ? tune.cols : pipe_default_cols(K, S, arith);
   RMA_CHECK_ARG(pipe_has_cols(K, S, arith, C), "no pipelined kernel with " << C
                                                    << " column waves for K=" << K << " S=" << S

@@ -8,6 +8,8 @@
 // per pass at 101120^2 K=10..24 -0.7..-7 % against the ring kernel (K=20
 // 68.69 vs 70.20 ms, K=24 79.03 vs 80.22); at 16384^2 K=10 / 12 slower
 // (+12 / +7 %). profiles/SUMMARY_r3.md section 8.
+// K = 17..19 and 21..23 also hold the six-cell uniform-factor kernel
+// (RMA_PIPE_CASE_U6; 216 / 254 VGPRs, no scratch).
 #include "stencil_pipe.h"
 
 namespace rma {
@@ -22,13 +24,13 @@ bool dispatch_r(int K, int S, int V, int ar, const PipeLaunch& a) {
   RMA_PIPE_CASE_U(14, 4, kArFast5Reg)
   RMA_PIPE_CASE_U(15, 4, kArFast5Reg)
   RMA_PIPE_CASE_U(16, 4, kArFast5Reg)
-  RMA_PIPE_CASE_U(17, 4, kArFast5Reg)
-  RMA_PIPE_CASE_U(18, 4, kArFast5Reg)
-  RMA_PIPE_CASE_U(19, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(17, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(18, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(19, 4, kArFast5Reg)
   // K = 20: stencil_pipe_r20.hip
-  RMA_PIPE_CASE_U(21, 4, kArFast5Reg)
-  RMA_PIPE_CASE_U(22, 4, kArFast5Reg)
-  RMA_PIPE_CASE_U(23, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(21, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(22, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(23, 4, kArFast5Reg)
   RMA_PIPE_CASE_U(24, 4, kArFast5Reg)
   return false;
 }

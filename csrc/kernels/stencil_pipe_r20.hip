@@ -5,6 +5,7 @@
 // instructions, another order: -0.7 % per K = 20 pass at 101376^2, same box,
 // two alternating rounds (66.40 vs 66.89 ms); at K = 24 the same strategy is
 // +0.4 % and max-ILP is worse at both (profiles/r6/sched_strategy_ab.md).
+// Also the six-cell uniform-factor kernel of K = 20 (218 VGPRs, no scratch).
 #include "stencil_pipe.h"
 
 namespace rma {
@@ -12,7 +13,7 @@ namespace pipe {
 
 bool dispatch_r20(int K, int S, int V, int ar, const PipeLaunch& a) {
   if (ar != kArFast5Reg) return false;
-  RMA_PIPE_CASE_U(20, 4, kArFast5Reg)
+  RMA_PIPE_CASE_U6(20, 4, kArFast5Reg)
   return false;
 }
 

@@ -146,6 +146,10 @@ DiffusionExecutor::DiffusionExecutor(double* T, double* T2, const double* iCp, i
       for (char& ch : pc)
         if (ch == '/') ch = ',';
       apply_cost_overrides(cost_, pc.empty() ? nullptr : pc.c_str());
+      cost_base_ = cost_;
+      // the row of the uniform-factor passes (scan_factor selects)
+      cost_uni_ = fast5() ? uniform_pass_costs(p.temporal, (double)nx * (double)ny) : cost_;
+      apply_cost_overrides(cost_uni_, pc.empty() ? nullptr : pc.c_str());
     }
     geom_.resize(p.temporal + 1);
     geom_ok_.assign(p.temporal + 1, 0);
@@ -278,6 +282,12 @@ void DiffusionExecutor::release_resources() {
 void DiffusionExecutor::scan_factor() {
   uniform_ = false;
   c0_ = 0.0;
+  std::fill(geom_ok_.begin(), geom_ok_.end(), 0);  // the strip step follows the verdict
+  if (!cost_base_.empty() && !direct_on_) cost_ = cost_base_;  // and the planner's row
+  const std::string cells = diag_value("pipe_cells");
+  RMA_CHECK_ARG(cells.empty() || cells == "4" || cells == "6",
+                "RMA_DIAG pipe_cells=" << cells << " (4 | 6)");
+  cells_ = cells.empty() ? 0 : cells == "4" ? 4 : 6;
   const std::string v = diag_value("uniform_factor");
   RMA_CHECK_ARG(v.empty() || v == "off", "RMA_DIAG uniform_factor=" << v << " (off)");
   // only the fast-math K-step passes have a uniform-factor kernel
@@ -302,6 +312,8 @@ void DiffusionExecutor::scan_factor() {
   if (h[0] != 0) return;
   uniform_ = true;
   std::memcpy(&c0_, &h[1], sizeof c0_);
+  // (direct-store halos price the field row: their frame launches run the field path)
+  if (!cost_base_.empty() && !direct_on_) cost_ = cost_uni_;
 }
 
 bool DiffusionExecutor::rescan_factor() {
@@ -331,7 +343,9 @@ const PassGeom& DiffusionExecutor::geometry(int K) {
     int vec = t.vec;
     if (t.kernel >= 9) {
       // the cells per lane the kernel will run (its strip step), not the request
-      vec = pipe_vec(K, t.stages, t.kernel - 9, nx_, t.vec, true);
+      // (six cells only for the uniform-factor launches, as the launcher resolves it)
+      vec = pipe_vec_uniform(K, t.stages, t.kernel - 9, nx_, t.vec, true,
+                             uniform_ && !direct_active());
       tw = (64 * vec - 2 * K) / vec * vec;
       th = t.chunk_rows;
     }
@@ -358,6 +372,15 @@ StencilTuning DiffusionExecutor::pass_tuning(int K, int part) const {
   t.nontemporal = p_.tune2.nontemporal;
   if (p_.chunk_rows2 > 0) t.chunk_rows = p_.chunk_rows2;
   if (K == 2 && !fast5()) t.unroll = p_.tune2.unroll;
+  // uniform 1/Cp without direct-store halos: six cells per lane (384-column
+  // windows) where the per-class table says so (plan.cpp pipe_uniform_cells: K =
+  // 17..24 on the 288 GB tile class, profiles/r8/six_cells.md). The launcher falls
+  // back to four cells where nx is odd, the depth has no six-cell kernel or a
+  // launch runs the field path. RMA_DIAG pipe_cells=4 | 6: never / on every tile
+  // (A/B runs, tests).
+  const bool six =
+      cells_ == 6 || (cells_ == 0 && pipe_uniform_cells(K, (double)nx_ * (double)ny_) == 6);
+  if (uniform_ && !direct_active() && six && (t.kernel == 12 || t.kernel == 22)) t.vec = 6;
   if (part == 0) return t;
   if (t.kernel >= 9 && part == 1) {
     // pipelined passes, wide y-frames (~2K rows, full width): the interior's
@@ -675,7 +698,7 @@ void DiffusionExecutor::set_direct(const std::array<DirectPeer, 8>& peers, uint6
   // fewer blocks per CU than the plain one (the register cap, stencil_pipe.h
   // pipe_kernel_dir) costs that much more per pass
   if (cost_base_.empty()) cost_base_ = cost_;
-  cost_ = cost_base_;
+  cost_ = uniform_ && !any && !cost_uni_.empty() ? cost_uni_ : cost_base_;
   if (any) {
     const bool al = ((reinterpret_cast<uintptr_t>(T_) | reinterpret_cast<uintptr_t>(T2_) |
                       reinterpret_cast<uintptr_t>(iCp_)) & 15) == 0;

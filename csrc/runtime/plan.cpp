@@ -207,7 +207,35 @@ constexpr double kCanon[kTables][25] = {
      2.784, 2.772, 2.798, 2.857, 3.333, 3.319, 3.364, 3.467, 5.660, 5.443, 5.489, 5.591},
     {0, 1.000, 1.079, 1.146, 1.067, 1.212, 1.178, 1.362, 1.398, 1.597, 1.755, 1.833, 1.885,
      2.306, 2.383, 2.491, 2.533, 2.863, 2.947, 3.079, 3.131, 4.643, 4.586, 4.713, 4.770}};
+
+// Uniform 1/Cp on the 288 GB tile class (cells >= 98304^2): the passes of K >=
+// 10 run piper's uniform-factor variant, K = 17..24 at six cells per lane
+// (pipe_uniform_cells). Pass times of one lease at 101120^2 (bench/pass_sweep.py
+// --exec-uniform 10-16 / --exec-uniform6 17-24, median of 5 interleaved rounds,
+// profiles/r8/six_cells.md sections 2 and 6) over that lease's one-step time
+// (39.415 ms; its field-path K = 24 pass gives 1.968 against kFast5's 1.962).
+// K = 1..9 have no uniform variant: the field-path entries.
+constexpr double kUniformCells = 98304.0 * 98304.0;
+constexpr double kUniform288[25] = {
+    0, 1.235, 1.230, 1.215, 1.163, 1.232, 1.210, 1.199, 1.126, 1.149, 0.903, 0.902, 0.905,
+    1.138, 1.079, 1.117, 1.142, 1.273, 1.280, 1.327, 1.399, 1.459, 1.505, 1.527, 1.546};
 }  // namespace
+
+int pipe_uniform_cells(int K, double cells) {
+  // six cells where the same-run sweep gained: every instantiated depth at
+  // 101120^2 (K = 17..24: -3.9 .. -10.1 % per pass). 8192^2 and 4096^2 lose
+  // (+2..13 %, +42..48 %: too few of the wider strips); 16384^2 gained at K = 17,
+  // 20, 21 but not at its K = 24 (-0.8 %) and was not swept at the other depths.
+  return cells >= kUniformCells && K >= 17 && K <= 24 ? 6 : 4;
+}
+
+std::vector<double> uniform_pass_costs(int kmax, double cells) {
+  if (cells < kUniformCells) return default_pass_costs(kmax, true, cells);
+  RMA_CHECK_ARG(kmax >= 1 && kmax <= 24, "kmax=" << kmax << " (tables cover 1..24)");
+  std::vector<double> c(kmax + 1, kInf);
+  for (int K = 1; K <= kmax; ++K) c[K] = kUniform288[K];
+  return c;
+}
 
 int pipe_chunk_rows(int K, int64_t ny, bool canonical) {
   if (ny < 1024) return 0;

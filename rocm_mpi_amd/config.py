@@ -38,6 +38,7 @@ DIAG_KEYS = {
     "pipe_fast": "pipe | pipe5: the LDS-ring fast kernel at every depth",
     "pass_costs": "K:cost/K:cost/...: planner cost overrides",
     "uniform_factor": "off: the 1/Cp field path also where 1/Cp is one value",
+    "pipe_cells": "4 | 6: uniform passes at four cells everywhere / six on every tile",
     # communication (C++)
     "rccl_data_blocking": "blocking RCCL data path of a non-blocking communicator",
     "rccl_graph": "allow hipGraph capture over RCCL",

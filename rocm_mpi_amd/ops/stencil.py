@@ -103,7 +103,9 @@ class StencilTuning:
     profiles/sweep_16k.md): rows per wave-task, rows whose loads are issued
     together, non-temporal bitmask (1: T2 stores, 2: 1/Cp loads), cells per
     lane (2 or 4; the fast5 ``pipe`` kernel also 5 at K = 16..20 when nx % 5 == 0, a
-    lab-library experiment, see ``native().pipe_vec``), and the kernel family ("march"
+    lab-library experiment, see ``native().pipe_vec``; ``piper`` / ``piper_nosb`` with
+    ``uniform`` also 6 at K = 17..24 for any even nx, ``native().pipe_vec_uniform``),
+    and the kernel family ("march"
     or the "lds" baseline).
     Bit 2 of the non-temporal mask also streams T loads (implies bits 0-1)."""
 
