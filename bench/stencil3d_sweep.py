@@ -9,7 +9,12 @@ times Diffusion3D's ``perf`` and ``ap`` variants at N^3 (the kernel against the
 torch expressions a user had before). ``--one`` runs a few launches of the
 default tuning and of the probes only (for a counter-collection run).
 
+``--temporal 2`` instead times one 2-step pass (csrc/kernels/stencil3d_tb.hip,
+every tb_rows x tb_chunk_z) against two launches of the one-step kernel at its
+shipped tuning, in the same interleaved rounds (profiles/diffusion3d_temporal.md).
+
     python bench/stencil3d_sweep.py --sizes 512,1024,1536 --ap 1024 --out sweep3d.json
+    python bench/stencil3d_sweep.py --temporal 2 --out sweep3d_tb.json
 """
 from __future__ import annotations
 
@@ -47,7 +52,33 @@ def sweep_size(n: int, a) -> dict:
         return bufs[flip[0]], bufs[flip[0] ^ 1]
 
     variants = {}
-    if a.one:
+    steps = {}  # time steps one call of a variant advances (default 1)
+    if a.temporal > 1:
+        K = a.temporal
+        tunings = []
+
+        def onestep_k():  # K launches of the one-step kernel at its shipped tuning
+            for _ in range(K):
+                dst, src = pair()
+                ops.stencil3d_step(dst, src, iCp, coef)
+
+        variants["onestep_x%d" % K] = (onestep_k, 24.0 * cells * K)
+        steps["onestep_x%d" % K] = K
+        tbs = [ops.Stencil3DTuning(tb_rows=r, tb_chunk_z=cz) for r in ops.TB_ROWS_3D
+               for cz in a.tb_chunk_z]
+        tbs += [ops.Stencil3DTuning(tb_nontemporal=m) for m in (1, 2, 3)]
+        tbs += [ops.Stencil3DTuning(xcd_remap=0)]
+        for tn in tbs:
+            name = (f"tb{K}_r{tn.tb_rows}_cz{tn.tb_chunk_z}_nt{tn.tb_nontemporal}"
+                    f"_x{tn.xcd_remap}")
+
+            def run_tb(tn=tn):
+                dst, src = pair()
+                ops.stencil3dk_step(K, dst, src, iCp, coef, tuning=tn)
+
+            variants[name] = (run_tb, 24.0 * cells)
+            steps[name] = K
+    elif a.one:
         tunings = [ops.Stencil3DTuning()]
     else:
         tunings = [ops.Stencil3DTuning(rows=r, unroll=u, vec=v, chunk_z=cz)
@@ -90,13 +121,19 @@ def sweep_size(n: int, a) -> dict:
     res = {}
     for k, (_, b) in variants.items():
         med = statistics.median(times[k])
+        nst = steps.get(k, 1)
         res[k] = {"median_ms": med, "min_ms": min(times[k]), "max_ms": max(times[k]),
-                  "GBps": b / med / 1e6, "T_eff_GBps": 24.0 * cells / med / 1e6}
+                  "GBps": b / med / 1e6, "T_eff_GBps": 24.0 * cells * nst / med / 1e6}
+        if a.temporal > 1:
+            res[k]["ms_per_step"] = med / nst
     tri, cp = res["roof_triad"]["median_ms"], res["roof_copy"]["GBps"]
     for k, r in res.items():
         if k.startswith("march"):
             r["vs_triad"] = tri / r["median_ms"]
             r["vs_copy_rate"] = r["GBps"] / cp
+        if k.startswith("tb"):  # > 1: the K-step pass is ahead of K one-step launches
+            r["vs_onestep"] = res["onestep_x%d" % a.temporal]["median_ms"] / r["median_ms"]
+            r["vs_triad"] = tri / r["median_ms"]  # the ceiling of a 24 B pass is 1
     del bufs, iCp
     torch.cuda.empty_cache()
     return res
@@ -126,6 +163,10 @@ def main(argv=None) -> int:
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--chunk-z", dest="chunk_z", default="0,32,128",
                     type=lambda v: [int(x) for x in v.split(",")])
+    ap.add_argument("--temporal", type=int, default=1, choices=[1, 2],
+                    help="2: the 2-step pass against two one-step launches")
+    ap.add_argument("--tb-chunk-z", dest="tb_chunk_z", default="0,16,64",
+                    type=lambda v: [int(x) for x in v.split(",")])
     ap.add_argument("--ap", type=int, default=0, help="cube size of the perf-versus-ap timing")
     ap.add_argument("--ap-steps", type=int, default=5)
     ap.add_argument("--one", action="store_true", help="default tuning and probes only")
@@ -141,7 +182,9 @@ def main(argv=None) -> int:
         for ms, k in best:
             r = report["sizes"][str(n)][k]
             print(f"{n:5d}^3 {k:40s} {ms:9.3f} ms  {r['GBps']:8.1f} GB/s"
-                  + (f"  {r['vs_triad']:.3f} of triad" if "vs_triad" in r else ""), flush=True)
+                  + (f"  {r['vs_triad']:.3f} of triad" if "vs_triad" in r else "")
+                  + (f"  {r['vs_onestep']:.3f} x one-step" if "vs_onestep" in r else ""),
+                  flush=True)
     if a.ap:
         report["perf_vs_ap"] = model_compare(a.ap, a.ap_steps)
         print("perf_vs_ap", json.dumps(report["perf_vs_ap"]), flush=True)

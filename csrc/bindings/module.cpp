@@ -235,6 +235,40 @@ PYBIND11_MODULE(_C, m) {
       py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
       py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true);
   m.def("stencil3d_has", &stencil3d_has, py::arg("rows"), py::arg("unroll"));
+  m.def(
+      "stencil3dk_boxes",
+      [](int K, uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
+         const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
+         int nontemporal, int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
+         int tb_nontemporal, uintptr_t stream, bool gpu) {
+        auto b = to_boxes(boxes);
+        if (gpu) {
+          Stencil3DTuning tn;
+          tn.rows = rows;
+          tn.unroll = unroll;
+          tn.vec = vec;
+          tn.nontemporal = nontemporal;
+          tn.chunk_z = chunk_z;
+          tn.xcd_remap = xcd_remap;
+          tn.tb_rows = tb_rows;
+          tn.tb_chunk_z = tb_chunk_z;
+          tn.tb_nontemporal = tb_nontemporal;
+          stencil3dk_boxes_gpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny,
+                               nz, b.data(), (int)b.size(), to_coef3(coef), tn, S(stream));
+        } else {
+          py::gil_scoped_release nogil;
+          stencil3dk_boxes_cpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny,
+                               nz, b.data(), (int)b.size(), to_coef3(coef));
+        }
+      },
+      py::arg("K"), py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("ny"),
+      py::arg("nz"), py::arg("boxes"), py::arg("coef"), py::arg("rows") = 4,
+      py::arg("unroll") = 2, py::arg("vec") = 2, py::arg("nontemporal") = 3,
+      py::arg("chunk_z") = 0, py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0,
+      py::arg("tb_chunk_z") = 0, py::arg("tb_nontemporal") = 0, py::arg("stream") = 0,
+      py::arg("gpu") = true);
+  m.def("stencil3dk_has", &stencil3dk_has, py::arg("K"));
+  m.def("stencil3dk_has_rows", &stencil3dk_has_rows, py::arg("rows"));
   m.def("init_gaussian3d", [](uintptr_t T, int64_t nx, int64_t ny, int64_t nz, const Geom3& g,
                               double lx, double ly, double lz, uintptr_t stream, bool gpu) {
     if (gpu)

@@ -189,6 +189,10 @@ struct Stencil3DTuning {
   int nontemporal = 3;  // bit 0: NT T2 stores; bit 1: NT 1/Cp loads
   int chunk_z = 0;      // planes one wave marches (0: 32, the measured default)
   int xcd_remap = 1;    // 1: each XCD takes a contiguous 1/8 of the blocks
+  // the K-step kernel (stencil3d_tb.hip) shares vec and xcd_remap and has its own
+  int tb_rows = 0;         // output rows per wave (0: the measured default, 4; 2 or 4)
+  int tb_chunk_z = 0;      // output planes one wave marches (0: the measured default, 32)
+  int tb_nontemporal = 0;  // bits as nontemporal; 0 measured 6-7 % ahead of 3 for this kernel
 };
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
@@ -201,6 +205,22 @@ void stencil3d_boxes_cpu(double* T2, const double* T, const double* iCp, int64_t
 // the argument checks both twins run before any work
 void validate_boxes(const double* T2, const double* T, int64_t nx, int64_t ny, int64_t nz,
                     const Box* boxes, int nboxes);
+
+// K steps per pass (temporal blocking, stencil3d_tb.hip): T2[b] = f^K(T)[b], the
+// intermediate levels being f on the interior [1,n-1)^3 and T on the six faces.
+// Bitwise equal to K full-interior calls of stencil3d_boxes_* followed by a crop
+// to the boxes. T2 != T; cells outside the boxes are not written. K = 1 forwards
+// to the one-step kernel; a K that stencil3dk_has() denies is an invalid
+// argument before any work. Every box runs the strip march (no thin-box path).
+bool stencil3dk_has(int K);
+bool stencil3dk_has_rows(int rows);  // Stencil3DTuning::tb_rows values instantiated
+void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                          int64_t ny, int64_t nz, const Box* boxes, int nboxes,
+                          const StencilCoef3& c, const Stencil3DTuning& tune, stream_t stream);
+// the one-step twin applied K times through two scratch arrays (any K >= 1)
+void stencil3dk_boxes_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                          int64_t ny, int64_t nz, const Box* boxes, int nboxes,
+                          const StencilCoef3& c);
 
 // Width (in cells) of one wave's x-strip in the march kernel; perf_hide rounds
 // its x-frame so the interior rect starts on a strip boundary.

@@ -113,6 +113,25 @@ void stencil3d_boxes_cpu(double* T2, const double* T, const double* iCp, int64_t
   }
 }
 
+// CPU twin of stencil3dk_boxes_gpu (stencil3d_tb.hip): no kernel code shared
+void stencil3dk_boxes_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                          int64_t ny, int64_t nz, const Box* boxes, int nboxes,
+                          const StencilCoef3& c) {
+  RMA_CHECK_ARG(K >= 1, "K=" << K);
+  validate_boxes(T2, T, nx, ny, nz, boxes, nboxes);
+  if (K == 1) {
+    stencil3d_boxes_cpu(T2, T, iCp, nx, ny, nz, boxes, nboxes, c);
+    return;
+  }
+  std::vector<double> a(T, T + nx * ny * nz), b(a);
+  const Box interior{1, nx - 1, 1, ny - 1, 1, nz - 1};
+  for (int j = 1; j < K; ++j) {  // levels 1..K-1 on the interior, T on the faces
+    stencil3d_boxes_cpu(b.data(), a.data(), iCp, nx, ny, nz, &interior, 1, c);
+    a.swap(b);
+  }
+  stencil3d_boxes_cpu(T2, a.data(), iCp, nx, ny, nz, boxes, nboxes, c);
+}
+
 bool fast5_ok(const StencilCoef& c) {
   const double ax = (-c.mlam) * c.rdx * c.rdx, ay = (-c.mlam) * c.rdy * c.rdy;
   return ax != 0.0 && std::isfinite(ax) && std::isfinite(ay) && std::isfinite(ay / ax) &&

@@ -1,0 +1,308 @@
+// K explicit 3D diffusion steps per HBM sweep (temporal blocking) for CDNA4
+// (gfx950): T2[b] = f^K(T)[b] on a list of boxes, the intermediate levels being
+// f on the interior [1,n-1)^3 and T on the six faces. Bitwise equal to K
+// launches of stencil3d.hip on the full interior followed by a crop to the
+// boxes (StencilCoef3's expression, compiled without contraction). K = 2 is
+// instantiated; the kernel is a template over K.
+//
+// Design (the z register march of stencil3d.hip, skewed in time):
+//   * Model traffic per pass: one read of T, one read of 1/Cp, one write of T2,
+//     24 B per cell for K steps.
+//   * One 64-lane wave owns an x-strip of 64*V cells and R output rows. It loads
+//     R + 2K rows of every plane (rows ya-K .. ya+R+K-1) and recomputes the lower
+//     levels at the band seams itself: no LDS, no barrier, waves independent.
+//     Level l lives on the rows [l, R+2K-l) of that window.
+//   * Along z the levels are skewed: when plane p of level 0 arrives, level l
+//     computes its plane p-l from the planes p-l-1, p-l, p-l+1 of level l-1, so
+//     plane p-K of level K is stored. Each level keeps three planes in registers,
+//     1/Cp one plane per level. A chunk loads K planes before and K planes after
+//     its output planes (the first two before the march starts).
+//   * In x a strip loads 64*V columns plus one edge column per side for level 0
+//     (lanes 0-31 the cell left of the strip, 32-63 the cell right of it), so
+//     level 1 is valid on the whole strip and level l on the columns
+//     [l-1, 64V-l]; x neighbours come from the adjacent lane. Strips advance by
+//     64*V - 2(K-1) columns (126 at V = 2, K = 2: even, a lane's pair stays
+//     16-byte aligned). At an array face every level is exact (the face cell
+//     keeps T), so a strip that touches it is valid up to it.
+//   * A level-l cell on an array face takes the level l-1 value (T) unchanged.
+//     Planes, rows and lanes past the array edge load clamped and store masked;
+//     what they compute feeds only masked cells. All offsets are 64-bit.
+//   * T2 stores and 1/Cp loads can be non-temporal (tb_nontemporal bits 0 and 1);
+//     plain accesses measured 6-7 % faster here, unlike in the one-step kernel,
+//     and are the default. Blocks are ordered per XCD (xcd_remap) as in the
+//     one-step kernel: four waves of a block own four adjacent bands of one strip.
+//   * Odd nx or a base off 16-byte alignment runs the same march with V = 1.
+//     Every box runs the strip march (no thin-box path).
+//
+// VGPRs / waves per SIMD at K = 2 (build's resource output; no AGPRs, no scratch):
+// (V, R) = (2, 2) 162 / 3, (2, 4) 230 / 2, (1, 2) 98 / 4, (1, 4) 132 / 3, the same
+// for every non-temporal mask. (2, 4) measured 8-13 % ahead of (2, 2)
+// (profiles/diffusion3d_temporal.md).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "rma/hip_check.h"
+#include "rma/kernels.h"
+#include "stencil_device.h"
+
+namespace rma {
+namespace {
+using namespace march;
+
+// defaults of Stencil3DTuning::tb_rows / tb_chunk_z = 0 (profiles/diffusion3d_temporal.md)
+constexpr int kTbDefaultRows = 4;
+constexpr int64_t kTbDefaultChunkZ = 32;
+
+struct BoxListK {
+  Box b[kMaxBoxes];
+  int64_t xa[kMaxBoxes];         // origin of strip 0 (a multiple of V)
+  int64_t strips[kMaxBoxes];
+  int64_t bands[kMaxBoxes];
+  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / waves per block)
+  int64_t chunk_z[kMaxBoxes];    // output planes per task
+  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
+  int n;
+};
+
+__device__ __forceinline__ double cell3k(double xl, double c, double xr, double up, double dn,
+                                         double bk, double fr, double ic,
+                                         const StencilCoef3& k) {
+  const double qxR = (k.mlam * (xr - c)) * k.rdx;
+  const double qxL = (k.mlam * (c - xl)) * k.rdx;
+  const double qyU = (k.mlam * (dn - c)) * k.rdy;
+  const double qyD = (k.mlam * (c - up)) * k.rdy;
+  const double qzF = (k.mlam * (fr - c)) * k.rdz;
+  const double qzB = (k.mlam * (c - bk)) * k.rdz;
+  return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
+}
+
+template <int K, int V, int R, bool NTS, bool NTL>
+__global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict__ T2,
+                                                              const double* __restrict__ T,
+                                                              const double* __restrict__ iCp,
+                                                              int64_t nx, int64_t ny, int64_t nz,
+                                                              BoxListK L, StencilCoef3 k,
+                                                              int remap) {
+  constexpr int NR = R + 2 * K;                 // rows of the level-0 window
+  constexpr int64_t kStep = kWave * V - 2 * (K - 1);  // strip advance
+  const int64_t b = remap ? xcd_remap(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int bi = 0;
+  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
+  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const Box box = L.b[bi];
+  const int64_t plane = nx * ny;
+  // block lb of a box: strip fastest, then the group of 4 bands, then the z chunk
+  const int64_t strip = lb % L.strips[bi];
+  const int64_t rest = lb / L.strips[bi];
+  const int64_t band = (rest % L.groups[bi]) * kWavesPerBlock + wave;
+  const int64_t zc = rest / L.groups[bi];
+  if (band >= L.bands[bi]) return;  // the whole wave
+  const int64_t xs = L.xa[bi] + strip * kStep;
+  const int64_t ya = box.y0 + band * R;
+  const int64_t za = box.z0 + zc * L.chunk_z[bi];
+  const int64_t zb = min(box.z1, za + L.chunk_z[bi]);
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t x = xs + (int64_t)lane * V;  // first cell of the lane
+  const int64_t xl = min(x, nx - V);         // clamped load column
+  const int64_t eidx = (lane < 32) ? max(xs - 1, (int64_t)0) : min(xs + kWave * V, nx - 1);
+  // columns on which level K is valid: all the way to an array face the strip touches
+  const int clo = xs == 0 ? 0 : K - 1;
+  const int chi = xs + kWave * V >= nx ? kWave * V - 1 : kWave * V - K;
+  bool m[V], xface[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const int c = lane * V + v;
+    m[v] = (x + v >= box.x0) && (x + v < box.x1) && c >= clo && c <= chi;
+    xface[v] = (x + v <= 0) || (x + v >= nx - 1);
+  }
+  const int nrows = (int)min((int64_t)R, box.y1 - ya);  // output rows inside the box
+  int64_t row[NR];  // element offset of window row j (global row ya-K+j, clamped)
+  bool rface[NR];   // that row lies on (or past) an array face
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int64_t g = ya - K + j;
+    row[j] = min(max(g, (int64_t)0), ny - 1) * nx;
+    rface[j] = g <= 0 || g >= ny - 1;
+  }
+
+  // Lv[l][s][j]: level l, plane slot s (planes p-l-2, p-l-1, p-l when plane p of
+  // level 0 is the newest), window row j. ic[l]: 1/Cp of plane p-l-1.
+  double Lv[K][3][NR][V], ic[K][NR][V];
+#pragma unroll
+  for (int l = 0; l < K; ++l)
+#pragma unroll
+    for (int j = 0; j < NR; ++j)
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        Lv[l][0][j][v] = Lv[l][1][j][v] = Lv[l][2][j][v] = 0.0;
+        ic[l][j][v] = 0.0;
+      }
+  int64_t p = za - K + 2;
+  {
+    const double* p0 = T + min(max(p - 2, (int64_t)0), nz - 1) * plane;
+    const double* p1 = T + min(max(p - 1, (int64_t)0), nz - 1) * plane;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      load_row<V>(Lv[0][0][j], p0 + row[j] + xl);
+      load_row<V>(Lv[0][1][j], p1 + row[j] + xl);
+    }
+  }
+  for (; p < zb + K; ++p) {
+    const int64_t pc = min(max(p - 1, (int64_t)0), nz - 1);  // centre plane of level 1
+    const double* pf = T + min(max(p, (int64_t)0), nz - 1) * plane;
+    double ed[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) load_row<V>(Lv[0][2][j], pf + row[j] + xl);
+#pragma unroll
+    for (int j = 1; j < NR - 1; ++j) {
+      load_row<V, NTL>(ic[0][j], iCp + pc * plane + row[j] + xl);
+      ed[j] = T[pc * plane + row[j] + eidx];
+    }
+#pragma unroll
+    for (int l = 1; l <= K; ++l) {
+      const int64_t z = p - l;  // plane this level computes
+      if (l == K && z < za) continue;  // warm-up: nothing to store yet
+      const bool zface = z <= 0 || z >= nz - 1;
+#pragma unroll
+      for (int j = l; j < NR - l; ++j) {
+        const double(&cu)[V] = Lv[l - 1][1][j];
+        const double(&up)[V] = Lv[l - 1][1][j - 1];
+        const double(&dn)[V] = Lv[l - 1][1][j + 1];
+        double left = __shfl_up(cu[V - 1], 1);
+        double right = __shfl_down(cu[0], 1);
+        if (l == 1) {
+          if (lane == 0) left = ed[j];
+          if (lane == kWave - 1) right = ed[j];
+        }
+        double res[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const double a = v == 0 ? left : cu[v == 0 ? 0 : v - 1];
+          const double c = v == V - 1 ? right : cu[v == V - 1 ? v : v + 1];
+          res[v] = cell3k(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v], Lv[l - 1][2][j][v],
+                          ic[l - 1][j][v], k);
+        }
+        if (l < K) {
+#pragma unroll
+          for (int v = 0; v < V; ++v)
+            Lv[l < K ? l : 0][2][j][v] = (zface || rface[j] || xface[v]) ? cu[v] : res[v];
+        } else if (j - K < nrows) {
+          store_row<V, NTS>(T2 + z * plane + row[j] + x, res, m);
+        }
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < K; ++l)
+#pragma unroll
+      for (int j = 0; j < NR; ++j)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          Lv[l][0][j][v] = Lv[l][1][j][v];
+          Lv[l][1][j][v] = Lv[l][2][j][v];
+        }
+#pragma unroll
+    for (int l = K - 1; l > 0; --l)
+#pragma unroll
+      for (int j = 0; j < NR; ++j)
+#pragma unroll
+        for (int v = 0; v < V; ++v) ic[l][j][v] = ic[l - 1][j][v];
+  }
+}
+
+int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, int R,
+                     int chunk_z) {
+  L = BoxListK{};
+  int64_t total = 0;
+  const int64_t step = (int64_t)kWave * V - 2 * (K - 1);
+  for (int i = 0; i < nboxes; ++i) {
+    const Box& b = boxes[i];
+    if (b.empty()) continue;
+    const int n = L.n++;
+    L.b[n] = b;
+    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
+    // strip 0 starts K-1 columns left of the box (its first valid column), on a
+    // multiple of V and never left of the array (valid from the face on there)
+    const int64_t x0 = std::max<int64_t>(b.x0 - (K - 1), 0);
+    L.xa[n] = x0 - (x0 % V);
+    const int64_t first = L.xa[n] == 0 ? 0 : L.xa[n] + (K - 1);  // first valid column
+    L.strips[n] = std::max<int64_t>(1, (b.x1 - first + step - 1) / step);
+    L.bands[n] = (nyb + R - 1) / R;
+    L.groups[n] = (L.bands[n] + kWavesPerBlock - 1) / kWavesPerBlock;
+    // each chunk re-reads 2K planes and recomputes K-1
+    L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : kTbDefaultChunkZ, nzb);
+    total += L.strips[n] * L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
+    L.block_end[n] = total;
+  }
+  return total;
+}
+
+template <int K, int V, int R>
+void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
+               int64_t nx, int64_t ny, int64_t nz, const BoxListK& L, const StencilCoef3& c,
+               int remap) {
+  const dim3 block(kBlock);
+  switch (nt & 3) {
+    case 0:
+      stencil3d_tb_kernel<K, V, R, false, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+                                                                        c, remap);
+      break;
+    case 1:
+      stencil3d_tb_kernel<K, V, R, true, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+                                                                       c, remap);
+      break;
+    case 2:
+      stencil3d_tb_kernel<K, V, R, false, true><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+                                                                       c, remap);
+      break;
+    default:
+      stencil3d_tb_kernel<K, V, R, true, true><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+                                                                      c, remap);
+  }
+}
+
+template <int K>
+void launch_k(int V, int R, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
+              const double* iCp, int64_t nx, int64_t ny, int64_t nz, const BoxListK& L,
+              const StencilCoef3& c, int remap) {
+  if (V == 2 && R == 2) launch_nt<K, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
+  else if (V == 2) launch_nt<K, 2, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
+  else if (R == 2) launch_nt<K, 1, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
+  else launch_nt<K, 1, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
+}
+
+}  // namespace
+
+bool stencil3dk_has(int K) { return K == 1 || K == 2; }
+bool stencil3dk_has_rows(int rows) { return rows == 2 || rows == 4; }
+
+void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                          int64_t ny, int64_t nz, const Box* boxes, int nboxes,
+                          const StencilCoef3& c, const Stencil3DTuning& tune, stream_t stream) {
+  RMA_CHECK_ARG(stencil3dk_has(K), "K=" << K << " steps per pass is not instantiated (1 or 2)");
+  if (K == 1) {
+    stencil3d_boxes_gpu(T2, T, iCp, nx, ny, nz, boxes, nboxes, c, tune, stream);
+    return;
+  }
+  validate_boxes(T2, T, nx, ny, nz, boxes, nboxes);
+  const int R = tune.tb_rows > 0 ? tune.tb_rows : kTbDefaultRows;
+  RMA_CHECK_ARG(stencil3dk_has_rows(R), "tb_rows=" << tune.tb_rows << " (0: default, 2 or 4)");
+  RMA_CHECK_ARG(tune.vec == 1 || tune.vec == 2, "vec=" << tune.vec << " (1 or 2)");
+  RMA_CHECK_ARG(tune.tb_nontemporal >= 0 && tune.tb_nontemporal <= 3,
+                "tb_nontemporal=" << tune.tb_nontemporal << " (bits 0 and 1)");
+  RMA_CHECK_ARG(tune.tb_chunk_z >= 0, "tb_chunk_z=" << tune.tb_chunk_z);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(T2) |
+                         reinterpret_cast<uintptr_t>(iCp)) & 15) == 0;
+  const int V = (aligned && nx % 2 == 0) ? tune.vec : 1;
+  BoxListK L{};
+  const int64_t total = plan_boxes_k(L, boxes, nboxes, K, V, R, tune.tb_chunk_z);
+  if (L.n == 0) return;
+  RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
+  launch_k<2>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal, T2, T, iCp, nx,
+              ny, nz, L, c, tune.xcd_remap ? 1 : 0);
+  RMA_HIP_LAUNCH_CHECK();
+}
+
+}  // namespace rma

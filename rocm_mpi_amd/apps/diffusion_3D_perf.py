@@ -37,7 +37,39 @@ def build_parser() -> argparse.ArgumentParser:
                     help="write the gathered mid-z plane as a heatmap PNG under output/")
     ap.add_argument("--json", action="store_true", help="print the run record as JSON (rank 0)")
     ap.add_argument("--check-every", type=int, default=0, help="NaN/Inf guard period")
+    ap.add_argument("--temporal", type=int, default=1, choices=[1, 2],
+                    help="steps per kernel pass (2: temporal blocking, grid overlap 4, perf only)")
     return ap
+
+
+def grid_line(model) -> str | None:
+    """The loud note when the solved global grid is not the reference's
+    (overlap 2K of K-step passes on a multi-rank grid); None when equal."""
+    from ..parallel import geometry as geo
+
+    g, cfg = model.g, model.cfg
+    run = tuple(g.nxyz_g)
+    ref = tuple(geo.n_global(n, g.dims[d], 2, int(g.periods[d]))
+                for d, n in enumerate((cfg.nx, cfg.ny, cfg.nz)))
+    if run == ref:
+        return None
+    dx_ref, dy_ref, dz_ref = cfg.lx / ref[0], cfg.ly / ref[1], cfg.lz / ref[2]
+    dt_ref = min(dx_ref * dx_ref, dy_ref * dy_ref, dz_ref * dz_ref) * cfg.Cp0 / cfg.lam / 6.1
+    return (f"[grid] global grid {run[0]}x{run[1]}x{run[2]} (overlap {g.overlaps[0]} for "
+            f"{cfg.temporal}-step passes), dx = {model.dx:.6e}, dt = {model.dt:.6e}; the "
+            f"reference's overlap 2 gives {ref[0]}x{ref[1]}x{ref[2]}, dx = {dx_ref:.6e}, dt = "
+            f"{dt_ref:.6e} (run with --temporal 1 to solve the reference's problem)")
+
+
+def plan_line(model, steps: int) -> str:
+    """What the timed loop runs (printed next to the reference's T_eff line)."""
+    import collections
+
+    plan = model.plan(steps)
+    passes = ", ".join(f"{n} x {k}" for k, n in sorted(collections.Counter(plan).items(),
+                                                         reverse=True))
+    return (f"[plan] {steps} timed steps in passes of {passes} step(s); canonical (bitwise = "
+            f"one-step updates); max {model.cfg.temporal} steps per pass (--temporal)")
 
 
 def visualise(model, outdir: str = "output") -> dict | None:
@@ -59,9 +91,17 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     cfg = Diffusion3DConfig(variant=a.variant, nx=a.nx, ny=a.ny, nz=a.nz, nt=a.nt, init=a.init,
                             dims=a.dims, periods=a.periods, transport=a.transport,
-                            device=a.device, check_every=a.check_every)
+                            device=a.device, check_every=a.check_every, temporal=a.temporal)
     model = Diffusion3D(cfg)
+    gline = grid_line(model) if a.temporal > 1 else None
+    if gline and model.g.me == 0:
+        print(gline, flush=True)
     res = model.run()
+    if a.temporal > 1:
+        if model.g.me == 0:
+            print(plan_line(model, res.timed_steps), flush=True)
+        res.extra["temporal"] = cfg.temporal
+        res.extra["overlaps"] = list(model.g.overlaps)
     if a.vis:
         info = visualise(model)
         if info is not None:

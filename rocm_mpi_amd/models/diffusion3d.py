@@ -14,9 +14,15 @@ Gaussian on cell centres or the counter-based random field.
 Both compute the canonical per-cell expression (``ops.StencilCoef3``), so their
 fields agree bitwise, with each other and across decompositions.
 
+``temporal=2`` (perf only) runs two steps per kernel pass (temporal blocking,
+csrc/kernels/stencil3d_tb.hip): bitwise the same field, half the passes and
+halo exchanges. As in 2D, K-step passes need width-K halos, i.e. grid overlap
+2K, which changes ``nx_g``, ``dx`` and ``dt`` on a multi-rank grid.
+
 Out of scope here (the 2D model has them): overlap of the boundary update with
-the interior, K-step passes, the native executor (every step is issued from
-Python), checkpointing and direct-store halos.
+the interior, passes deeper than two steps, a pass planner and the native
+executor (every pass is issued from Python), checkpointing and direct-store
+halos.
 """
 from __future__ import annotations
 
@@ -53,6 +59,7 @@ class Diffusion3DConfig:
     check_every: int = 0  # NaN/Inf guard period (0 = off)
     quiet: bool = False
     tuning: ops.Stencil3DTuning | None = None
+    temporal: int = 1  # steps per kernel pass (ops.TEMPORAL_3D), perf only
 
     def validate(self) -> None:
         if self.variant not in VARIANTS3D:
@@ -63,6 +70,10 @@ class Diffusion3DConfig:
             raise ValueError("nx, ny, nz >= 3 required")
         if self.nt < 1:
             raise ValueError("nt >= 1 required")
+        if self.temporal not in ops.TEMPORAL_3D:
+            raise ValueError(f"temporal must be one of {ops.TEMPORAL_3D}")
+        if self.temporal > 1 and self.variant != "perf":
+            raise ValueError("temporal blocking applies to the perf variant")
 
 
 class Diffusion3D:
@@ -75,6 +86,10 @@ class Diffusion3D:
         if not gg.grid_is_initialized():
             kw = dict(grid_kwargs or {})
             kw.setdefault("quiet", cfg.quiet)
+            if cfg.temporal > 1:  # width-K halos need overlap 2K (IGG: ol >= 2*hw)
+                K = cfg.temporal
+                kw.setdefault("overlaps", (2 * K, 2 * K, 2 * K))
+                kw.setdefault("halowidths", (K, K, K))
             gg.init_global_grid(cfg.nx, cfg.ny, cfg.nz, dimx=cfg.dims[0], dimy=cfg.dims[1],
                                 dimz=cfg.dims[2], periodx=cfg.periods[0], periody=cfg.periods[1],
                                 periodz=cfg.periods[2], transport=cfg.transport,
@@ -86,6 +101,12 @@ class Diffusion3D:
         if tuple(g.nxyz) != (cfg.nx, cfg.ny, cfg.nz):
             raise ValueError(f"global grid local size {g.nxyz} != config "
                              f"{(cfg.nx, cfg.ny, cfg.nz)}")
+        if cfg.temporal > 1:
+            K = cfg.temporal
+            if any(max(g.neighbors[d]) >= 0 and g.overlaps[d] < 2 * K for d in (0, 1, 2)):
+                raise ValueError(f"temporal={K} needs grid overlaps >= {2 * K} "
+                                 f"(init_global_grid(overlaps=({2 * K},{2 * K},{2 * K}), "
+                                 f"halowidths=({K},{K},{K})))")
         self.device = g.device
         nx, ny, nz = cfg.nx, cfg.ny, cfg.nz
         self.dx, self.dy, self.dz = cfg.lx / gg.nx_g(), cfg.ly / gg.ny_g(), cfg.lz / gg.nz_g()
@@ -128,16 +149,36 @@ class Diffusion3D:
         return self.T
 
     # ------------------------------------------------------------------
+    def owned_box(self, k: int) -> tuple:
+        """Cells a k-step pass writes: next to a neighbour the k cells [0,k) are
+        halo (refreshed by the exchange), elsewhere the boundary cell 0 stays."""
+        nb, n = self.g.neighbors, (self.cfg.nx, self.cfg.ny, self.cfg.nz)
+        box = []
+        for d in (0, 1, 2):
+            box += [k if nb[d][0] >= 0 else 1, n[d] - (k if nb[d][1] >= 0 else 1)]
+        return tuple(box)
+
+    def plan(self, n: int) -> list:
+        """Passes step(n) runs: n // K passes of K steps, the rest one step each."""
+        K = self.cfg.temporal
+        return [K] * (int(n) // K) + [1] * (int(n) % K)
+
     def step(self, n: int = 1) -> None:
         """Advance n time steps (asynchronous on a GPU)."""
-        for _ in range(int(n)):
-            if self.cfg.variant == "perf":
-                ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, tuning=self.cfg.tuning)
-                self.T, self.T2 = self.T2, self.T
-                update_halo_(self.T)
-            else:
+        if self.cfg.variant != "perf":
+            for _ in range(int(n)):
                 self._step_ap()
-            self.steps_done += 1
+                self.steps_done += 1
+            return
+        for k in self.plan(n):
+            if k == 1:
+                ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, tuning=self.cfg.tuning)
+            else:
+                ops.stencil3dk_step(k, self.T2, self.T, self.iCp, self.coef, [self.owned_box(k)],
+                                    tuning=self.cfg.tuning)
+            self.T, self.T2 = self.T2, self.T
+            update_halo_(self.T)
+            self.steps_done += k
 
     def _step_ap(self) -> None:
         """The canonical update as torch expressions (same operation order)."""
@@ -209,8 +250,38 @@ class Diffusion3D:
         return res
 
     def gather_interior(self, root: int = 0):
-        """The halo-stripped fields of all ranks assembled on root (None elsewhere)."""
-        return gather_(self.field[1:-1, 1:-1, 1:-1].contiguous(), None, root)
+        """The global field without its boundary cells assembled on root (None
+        elsewhere): every rank contributes the cells it owns, each global cell
+        once whatever the overlap."""
+        g = self.g
+        if all(o == 2 for o in g.overlaps):  # equal shares: the reference's gather!
+            return gather_(self.field[1:-1, 1:-1, 1:-1].contiguous(), None, root)
+        parts = g.comm.gather(self.field.contiguous(), root)
+        if g.me != root:
+            return None
+        n = (self.cfg.nx, self.cfg.ny, self.cfg.nz)
+
+        def owned(c: int, d: int) -> tuple:
+            """Local [lo, hi) of the cells the rank at coordinate c owns along d."""
+            ol = g.overlaps[d]
+            if g.periods[d]:  # n - ol distinct cells per rank, the grid's first is a ghost
+                return 1, 1 + n[d] - ol
+            # the overlap is split between the two neighbours; a physical face loses 1 cell
+            return (ol // 2 if c > 0 else 1), n[d] - ((ol - ol // 2) if c < g.dims[d] - 1 else 1)
+
+        size = [sum(hi - lo for lo, hi in (owned(c, d) for c in range(g.dims[d])))
+                for d in (0, 1, 2)]
+        out = torch.empty(size[::-1], dtype=self.field.dtype)
+        for r, part in enumerate(parts):
+            c = g.topo.coords(r)
+            src, dst = [], []
+            for d in (2, 1, 0):
+                lo, hi = owned(c[d], d)
+                start = sum(b - a for a, b in (owned(cc, d) for cc in range(c[d])))
+                src.append(slice(lo, hi))
+                dst.append(slice(start, start + hi - lo))
+            out[tuple(dst)] = part[tuple(src)].to(out.device)
+        return out
 
     def close(self) -> None:
         self.synchronize()

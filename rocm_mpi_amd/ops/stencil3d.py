@@ -47,7 +47,12 @@ class Stencil3DTuning:
     the y-band a wave keeps in registers (2, 4, 8), planes per march iteration
     (1 or 2; 1 with 8 rows), cells per lane (2: 16-byte accesses, 1: scalar),
     non-temporal bitmask (1: T2 stores, 2: 1/Cp loads), planes per wave task
-    (0: the measured default, 32) and the per-XCD block order."""
+    (0: the measured default, 32) and the per-XCD block order. The K-step kernel
+    (``stencil3dk_step``, csrc/kernels/stencil3d_tb.hip) shares vec and xcd_remap
+    and has its own output rows per wave (``tb_rows``: 2, 4), output planes per
+    wave task (``tb_chunk_z``) and non-temporal bitmask (``tb_nontemporal``); 0 is
+    the measured default of each (4 rows, 32 planes, plain accesses:
+    profiles/diffusion3d_temporal.md)."""
 
     rows: int = 4
     unroll: int = 2
@@ -55,10 +60,17 @@ class Stencil3DTuning:
     nontemporal: int = 3
     chunk_z: int = 0
     xcd_remap: int = 1
+    tb_rows: int = 0
+    tb_chunk_z: int = 0
+    tb_nontemporal: int = 0
 
 
 # every (rows, unroll) the launcher instantiates
 TUNINGS_3D = ((2, 1), (2, 2), (4, 1), (4, 2), (8, 1))
+# steps per pass stencil3dk_step runs (csrc/kernels/stencil3d_tb.hip stencil3dk_has)
+# and the output rows per wave its launcher instantiates
+TEMPORAL_3D = (1, 2)
+TB_ROWS_3D = (2, 4)
 
 
 @dataclass
@@ -158,6 +170,60 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
                                  4, 1, 2, 0, 0, 0, 0, False)
     else:
         stencil3d_torch(T2, T, iCp, coef, boxes)
+
+
+def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor,
+                    coef: StencilCoef3, boxes: Sequence[Box] | None = None,
+                    tuning: Stencil3DTuning | None = None) -> None:
+    """K explicit 3D diffusion steps in one pass: T2[b] = f^K(T)[b] on every box
+    (default: the interior), the intermediate levels being f on the interior and
+    T on the six faces. Bitwise equal to K full-interior ``stencil3d_step`` calls
+    cropped to the boxes; cells outside the boxes keep T2's values."""
+    K = int(K)
+    if K not in TEMPORAL_3D:
+        raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
+    if K == 1:
+        stencil3d_step(T2, T, iCp, coef, boxes, tuning)
+        return
+    check_field("T", T)
+    if T.dim() != 3:
+        raise ValueError(f"T must be a (nz, ny, nx) field, got shape {tuple(T.shape)}")
+    nz, ny, nx = T.shape
+    if min(nx, ny, nz) < 3:
+        raise ValueError(f"nx, ny, nz >= 3 required, got (nz, ny, nx) = {tuple(T.shape)}")
+    check_field("T2", T2, (nz, ny, nx), T.device)
+    check_field("iCp", iCp, (nz, ny, nx), T.device)
+    if _overlap(T2, T):
+        raise ValueError("T2 must not alias T (double buffering)")
+    boxes = validate_boxes(boxes if boxes is not None else [interior_box(nx, ny, nz)],
+                           nx, ny, nz)
+    if not boxes:
+        return
+    coef = StencilCoef3(*coef)
+    if T.is_cuda:
+        tn = tuning or Stencil3DTuning()
+        native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
+                                  tuple(coef), int(tn.rows), int(tn.unroll), int(tn.vec),
+                                  int(tn.nontemporal), int(tn.chunk_z), int(tn.xcd_remap),
+                                  int(tn.tb_rows), int(tn.tb_chunk_z), int(tn.tb_nontemporal),
+                                  stream_handle(T), True)
+    elif has_native():
+        native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
+                                  tuple(coef), 4, 1, 2, 0, 0, 0, 0, 0, 0, 0, False)
+    else:
+        stencil3dk_torch(K, T2, T, iCp, coef, boxes)
+
+
+def stencil3dk_torch(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor,
+                     c: StencilCoef3, boxes: Iterable[Box]) -> None:
+    """Pure-torch twin of the K-step pass: K - 1 full-interior steps through two
+    clones of T (the faces keep T), then the last step on the boxes."""
+    nz, ny, nx = T.shape
+    a, b = T.clone(), T.clone()
+    for _ in range(K - 1):
+        stencil3d_torch(b, a, iCp, c, [interior_box(nx, ny, nz)])
+        a, b = b, a
+    stencil3d_torch(T2, a, iCp, c, boxes)
 
 
 def _check3(name: str, t: torch.Tensor):
