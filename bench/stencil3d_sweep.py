@@ -13,12 +13,20 @@ default tuning and of the probes only (for a counter-collection run).
 every tb_rows x tb_chunk_z) against two launches of the one-step kernel at its
 shipped tuning, in the same interleaved rounds (profiles/diffusion3d_temporal.md).
 
+``--uniform`` also times the uniform-1/Cp variant of every tuning (16 B per cell:
+the factor is a kernel argument, the array is not read), each right after its
+field-path twin in the same rounds, and reports ``vs_field`` = field median /
+uniform median (profiles/diffusion3d_uniform.md); with ``--temporal 2`` the same
+for the two-step pass. ``spread`` = (max - min) / median over the rounds.
+
     python bench/stencil3d_sweep.py --sizes 512,1024,1536 --ap 1024 --out sweep3d.json
     python bench/stencil3d_sweep.py --temporal 2 --out sweep3d_tb.json
+    python bench/stencil3d_sweep.py --uniform --out sweep3d_uni.json
 """
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import statistics
@@ -78,6 +86,13 @@ def sweep_size(n: int, a) -> dict:
 
             variants[name] = (run_tb, 24.0 * cells)
             steps[name] = K
+            if a.uniform:
+                def run_tb_uni(tn=dataclasses.replace(tn, uniform=True, uniform_value=1.0)):
+                    dst, src = pair()
+                    ops.stencil3dk_step(K, dst, src, iCp, coef, tuning=tn)
+
+                variants[name + "_uni"] = (run_tb_uni, 16.0 * cells)
+                steps[name + "_uni"] = K
     elif a.one:
         tunings = [ops.Stencil3DTuning()]
     else:
@@ -94,6 +109,12 @@ def sweep_size(n: int, a) -> dict:
             ops.stencil3d_step(dst, src, iCp, coef, tuning=tn)
 
         variants[name] = (run, 24.0 * cells)
+        if a.uniform:
+            def run_uni(tn=dataclasses.replace(tn, uniform=True, uniform_value=1.0)):
+                dst, src = pair()
+                ops.stencil3d_step(dst, src, iCp, coef, tuning=tn)
+
+            variants[name + "_uni"] = (run_uni, 16.0 * cells)
 
     def triad():
         dst, src = pair()
@@ -123,7 +144,8 @@ def sweep_size(n: int, a) -> dict:
         med = statistics.median(times[k])
         nst = steps.get(k, 1)
         res[k] = {"median_ms": med, "min_ms": min(times[k]), "max_ms": max(times[k]),
-                  "GBps": b / med / 1e6, "T_eff_GBps": 24.0 * cells * nst / med / 1e6}
+                  "GBps": b / med / 1e6, "T_eff_GBps": 24.0 * cells * nst / med / 1e6,
+                  "spread": (max(times[k]) - min(times[k])) / med}
         if a.temporal > 1:
             res[k]["ms_per_step"] = med / nst
     tri, cp = res["roof_triad"]["median_ms"], res["roof_copy"]["GBps"]
@@ -134,6 +156,8 @@ def sweep_size(n: int, a) -> dict:
         if k.startswith("tb"):  # > 1: the K-step pass is ahead of K one-step launches
             r["vs_onestep"] = res["onestep_x%d" % a.temporal]["median_ms"] / r["median_ms"]
             r["vs_triad"] = tri / r["median_ms"]  # the ceiling of a 24 B pass is 1
+        if k.endswith("_uni"):  # > 1: the uniform variant is ahead; the traffic model allows 1.5
+            r["vs_field"] = res[k[:-4]]["median_ms"] / r["median_ms"]
     del bufs, iCp
     torch.cuda.empty_cache()
     return res
@@ -170,6 +194,8 @@ def main(argv=None) -> int:
     ap.add_argument("--ap", type=int, default=0, help="cube size of the perf-versus-ap timing")
     ap.add_argument("--ap-steps", type=int, default=5)
     ap.add_argument("--one", action="store_true", help="default tuning and probes only")
+    ap.add_argument("--uniform", action="store_true",
+                    help="also the uniform-1/Cp variant of every tuning (vs_field)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -183,7 +209,9 @@ def main(argv=None) -> int:
             r = report["sizes"][str(n)][k]
             print(f"{n:5d}^3 {k:40s} {ms:9.3f} ms  {r['GBps']:8.1f} GB/s"
                   + (f"  {r['vs_triad']:.3f} of triad" if "vs_triad" in r else "")
-                  + (f"  {r['vs_onestep']:.3f} x one-step" if "vs_onestep" in r else ""),
+                  + (f"  {r['vs_onestep']:.3f} x one-step" if "vs_onestep" in r else "")
+                  + (f"  {r['vs_field']:.3f} x field" if "vs_field" in r else "")
+                  + f"  spread {r['spread']:.3f}",
                   flush=True)
     if a.ap:
         report["perf_vs_ap"] = model_compare(a.ap, a.ap_steps)

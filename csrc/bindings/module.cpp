@@ -212,10 +212,13 @@ PYBIND11_MODULE(_C, m) {
       "stencil3d_boxes",
       [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
-         int nontemporal, int chunk_z, int xcd_remap, uintptr_t stream, bool gpu) {
+         int nontemporal, int chunk_z, int xcd_remap, uintptr_t stream, bool gpu, bool uniform,
+         double uniform_value) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
+          tn.uniform = uniform;
+          tn.uniform_value = uniform_value;
           tn.rows = rows;
           tn.unroll = unroll;
           tn.vec = vec;
@@ -233,17 +236,32 @@ PYBIND11_MODULE(_C, m) {
       py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
       py::arg("boxes"), py::arg("coef"), py::arg("rows") = 4, py::arg("unroll") = 2,
       py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
-      py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true);
+      py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true,
+      py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
+  // cells per lane a GPU launch with these arrays runs (stencil3d_vec)
+  m.def(
+      "stencil3d_vec",
+      [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int vec, bool uniform) {
+        Stencil3DTuning tn;
+        tn.vec = vec;
+        tn.uniform = uniform;
+        return stencil3d_vec(P<const double>(T2), P<const double>(T), P<const double>(iCp), nx,
+                             tn);
+      },
+      py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("vec") = 2,
+      py::arg("uniform") = false);
   m.def("stencil3d_has", &stencil3d_has, py::arg("rows"), py::arg("unroll"));
   m.def(
       "stencil3dk_boxes",
       [](int K, uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
-         int tb_nontemporal, uintptr_t stream, bool gpu) {
+         int tb_nontemporal, uintptr_t stream, bool gpu, bool uniform, double uniform_value) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
+          tn.uniform = uniform;
+          tn.uniform_value = uniform_value;
           tn.rows = rows;
           tn.unroll = unroll;
           tn.vec = vec;
@@ -266,9 +284,25 @@ PYBIND11_MODULE(_C, m) {
       py::arg("unroll") = 2, py::arg("vec") = 2, py::arg("nontemporal") = 3,
       py::arg("chunk_z") = 0, py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0,
       py::arg("tb_chunk_z") = 0, py::arg("tb_nontemporal") = 0, py::arg("stream") = 0,
-      py::arg("gpu") = true);
+      py::arg("gpu") = true, py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
   m.def("stencil3dk_has", &stencil3dk_has, py::arg("K"));
   m.def("stencil3dk_has_rows", &stencil3dk_has_rows, py::arg("rows"));
+  // Cells of A[0, n) whose bit pattern differs from A[0]'s. GPU: out2 is device
+  // memory (two 64-bit words: the count is added to out2[0], zero it on the same
+  // stream first; out2[1] = A[0]'s bits), nothing synchronises, returns 0. CPU:
+  // returns the count.
+  m.def(
+      "count_differing",
+      [](uintptr_t A, int64_t n, uintptr_t out2, uintptr_t stream, bool gpu) -> int64_t {
+        if (gpu) {
+          count_differing_gpu(P<const double>(A), n, P<uint64_t>(out2), S(stream));
+          return 0;
+        }
+        py::gil_scoped_release nogil;
+        return count_differing_cpu(P<const double>(A), n);
+      },
+      py::arg("A"), py::arg("n"), py::arg("out2") = 0, py::arg("stream") = 0,
+      py::arg("gpu") = true);
   m.def("init_gaussian3d", [](uintptr_t T, int64_t nx, int64_t ny, int64_t nz, const Geom3& g,
                               double lx, double ly, double lz, uintptr_t stream, bool gpu) {
     if (gpu)

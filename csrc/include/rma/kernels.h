@@ -193,9 +193,21 @@ struct Stencil3DTuning {
   int tb_rows = 0;         // output rows per wave (0: the measured default, 4; 2 or 4)
   int tb_chunk_z = 0;      // output planes one wave marches (0: the measured default, 32)
   int tb_nontemporal = 0;  // bits as nontemporal; 0 measured 6-7 % ahead of 3 for this kernel
+  // 1/Cp is bit-for-bit the one value uniform_value in every cell (the caller
+  // vouches for it; Diffusion3D scans the array): both kernels then run their
+  // uniform-factor variant, which takes the value as an argument and never
+  // reads the array (16 instead of 24 bytes per cell and pass), bitwise equal
+  // to the field path. Every launch has the variant; bit 1 of nontemporal /
+  // tb_nontemporal is accepted and has nothing to act on.
+  bool uniform = false;
+  double uniform_value = 0.0;
 };
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
+// Cells per lane both 3D launchers run: tune.vec with even nx and 16-byte
+// aligned T and T2 (and iCp, unless tune.uniform: the array is not read), else 1.
+int stencil3d_vec(const double* T2, const double* T, const double* iCp, int64_t nx,
+                  const Stencil3DTuning& tune);
 
 void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
                          int64_t nz, const Box* boxes, int nboxes, const StencilCoef3& c,

@@ -28,9 +28,14 @@
 //     end of a band likewise (wave-uniform). All offsets are 64-bit.
 //   * Odd nx or a base off 16-byte alignment runs the same march with V = 1.
 //     Boxes at most 8 cells wide (frame faces) run one thread per row.
+//   * Uniform 1/Cp (Stencil3DTuning::uniform, template flag Uni): the factor is a
+//     kernel argument, the array is never dereferenced and no ic registers are
+//     held: 16 B/cell. The same expression in the same order, so bitwise the
+//     field path's result. Bit 1 of nontemporal has nothing to act on there.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "rma/hip_check.h"
 #include "rma/kernels.h"
@@ -62,6 +67,10 @@ __device__ __forceinline__ double cell3(double xl, double c, double xr, double u
   return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
 }
 
+// 1/Cp as the kernels take it: the array, or with Uni its one value
+template <bool Uni>
+using Factor = std::conditional_t<Uni, double, const double* __restrict__>;
+
 // Addresses and masks of one wave task, constant along the march.
 template <int V, int R>
 struct Task {
@@ -77,13 +86,12 @@ struct Task {
 
 // UU planes z .. z+UU-1: P[0] / P[1] hold the own rows of planes z-1 / z on
 // entry and of planes z+UU-1 / z+UU on exit.
-template <int V, int R, int UU, int NP, bool NTS, bool NTL>
+template <int V, int R, int UU, int NP, bool NTS, bool NTL, bool Uni>
 __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restrict__ T2,
-                                        const double* __restrict__ T,
-                                        const double* __restrict__ iCp, const Task<V, R>& t,
-                                        int64_t z, const StencilCoef3& k) {
+                                        const double* __restrict__ T, Factor<Uni> iCp,
+                                        const Task<V, R>& t, int64_t z, const StencilCoef3& k) {
   static_assert(UU + 2 <= NP, "plane registers");
-  double H[UU][2][V], ic[UU][R][V], ed[UU][R];
+  double H[UU][2][V], ic[Uni ? 1 : UU][Uni ? 1 : R][V], ed[UU][R];
 #pragma unroll
   for (int u = 0; u < UU; ++u) {
     const double* pc = T + (z + u) * t.plane;
@@ -91,7 +99,7 @@ __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restric
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       load_row<V>(P[u + 2][r], pn + t.row[r] + t.xl);
-      load_row<V, NTL>(ic[u][r], iCp + (z + u) * t.plane + t.row[r] + t.xl);
+      if constexpr (!Uni) load_row<V, NTL>(ic[u][r], iCp + (z + u) * t.plane + t.row[r] + t.xl);
       ed[u][r] = pc[t.row[r] + t.eidx];
     }
     load_row<V>(H[u][0], pc + t.halo[0] + t.xl);
@@ -113,7 +121,9 @@ __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restric
       for (int v = 0; v < V; ++v) {
         const double xl = v == 0 ? left : cu[v == 0 ? 0 : v - 1];
         const double xr = v == V - 1 ? right : cu[v == V - 1 ? v : v + 1];
-        res[v] = cell3(xl, cu[v], xr, up[v], dn[v], P[u][r][v], P[u + 2][r][v], ic[u][r][v], k);
+        double f;
+        if constexpr (Uni) f = iCp; else f = ic[u][r][v];
+        res[v] = cell3(xl, cu[v], xr, up[v], dn[v], P[u][r][v], P[u + 2][r][v], f, k);
       }
       if (r < t.nrows) store_row<V, NTS>(T2 + (z + u) * t.plane + t.row[r] + t.x, res, t.m);
     }
@@ -131,10 +141,13 @@ __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restric
 // VGPRs / waves per SIMD at V = 2 (build's resource output): (R, U) = (2, 1) 78 / 6,
 // (2, 2) 139 / 3, (4, 1) 134 / 3, (4, 2) 227 / 2, (8, 1) 239 / 2; no scratch. Capping
 // (2, 2) and (4, 1) at the 128 registers of 4 waves spills 12-28 bytes per lane.
-template <int V, int R, int U, bool NTS, bool NTL>
+// With Uni (either store setting; no AGPRs, no scratch): V = 2 (2, 1) 70 / 7, (2, 2) 115 / 4,
+// (4, 1) 110 / 4, (4, 2) 179 / 2, (8, 1) 191 / 2; V = 1 (2, 1) 52 / 8, (2, 2) 88 / 5,
+// (4, 1) 70 / 7, (4, 2) 137 / 3, (8, 1) 135 / 3.
+template <int V, int R, int U, bool NTS, bool NTL, bool Uni = false>
 __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restrict__ T2,
                                                                  const double* __restrict__ T,
-                                                                 const double* __restrict__ iCp,
+                                                                 Factor<Uni> iCp,
                                                                  int64_t nx, int64_t ny,
                                                                  BoxList L, StencilCoef3 k,
                                                                  int remap) {
@@ -154,8 +167,10 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
     const int64_t z = box.z0 + i / rows, y = box.y0 + i % rows;
     const int64_t o = z * plane + y * nx;
     for (int64_t x = box.x0; x < box.x1; ++x) {
+      double f;
+      if constexpr (Uni) f = iCp; else f = iCp[o + x];
       const double v = cell3(T[o + x - 1], T[o + x], T[o + x + 1], T[o - nx + x], T[o + nx + x],
-                             T[o - plane + x], T[o + plane + x], iCp[o + x], k);
+                             T[o - plane + x], T[o + plane + x], f, k);
       if constexpr (NTS) {
         __builtin_nontemporal_store(v, T2 + o + x);
       } else {
@@ -196,9 +211,9 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
     load_row<V>(P[1][r], T + za * plane + t.row[r] + t.xl);
   }
   int64_t z = za;
-  for (; z + U <= zb; z += U) z_steps<V, R, U, U + 2, NTS, NTL>(P, T2, T, iCp, t, z, k);
+  for (; z + U <= zb; z += U) z_steps<V, R, U, U + 2, NTS, NTL, Uni>(P, T2, T, iCp, t, z, k);
   if constexpr (U > 1) {
-    for (; z < zb; ++z) z_steps<V, R, 1, U + 2, NTS, NTL>(P, T2, T, iCp, t, z, k);
+    for (; z < zb; ++z) z_steps<V, R, 1, U + 2, NTS, NTL, Uni>(P, T2, T, iCp, t, z, k);
   }
 }
 
@@ -234,8 +249,18 @@ int64_t plan_boxes(BoxList& L, const Box* boxes, int nboxes, int V, int R, int c
 
 template <int V, int R, int U>
 void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-               int64_t nx, int64_t ny, const BoxList& L, const StencilCoef3& c, int remap) {
+               int64_t nx, int64_t ny, const BoxList& L, const StencilCoef3& c, int remap,
+               bool uni, double fac) {
   const dim3 block(kBlock);
+  if (uni) {  // the 1/Cp-load bit has nothing to act on
+    if (nt & 1)
+      stencil3d_march_kernel<V, R, U, true, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+                                                                                L, c, remap);
+    else
+      stencil3d_march_kernel<V, R, U, false, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx,
+                                                                                 ny, L, c, remap);
+    return;
+  }
   switch (nt & 3) {
     case 0:
       stencil3d_march_kernel<V, R, U, false, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
@@ -258,18 +283,26 @@ void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, co
 template <int V>
 void launch_ru(int R, int U, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
                const double* iCp, int64_t nx, int64_t ny, const BoxList& L,
-               const StencilCoef3& c, int remap) {
-  if (R == 2 && U == 1) launch_nt<V, 2, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap);
-  else if (R == 2) launch_nt<V, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap);
-  else if (R == 4 && U == 1) launch_nt<V, 4, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap);
-  else if (R == 4) launch_nt<V, 4, 2>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap);
-  else launch_nt<V, 8, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap);
+               const StencilCoef3& c, int remap, bool uni, double fac) {
+  if (R == 2 && U == 1) launch_nt<V, 2, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else if (R == 2) launch_nt<V, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else if (R == 4 && U == 1) launch_nt<V, 4, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else if (R == 4) launch_nt<V, 4, 2>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else launch_nt<V, 8, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
 }
 
 }  // namespace
 
 bool stencil3d_has(int rows, int unroll) {
   return ((rows == 2 || rows == 4) && (unroll == 1 || unroll == 2)) || (rows == 8 && unroll == 1);
+}
+
+int stencil3d_vec(const double* T2, const double* T, const double* iCp, int64_t nx,
+                  const Stencil3DTuning& tune) {
+  // the uniform variant does not read 1/Cp: its alignment does not count
+  const bool aligned = ((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(T2) |
+                         (tune.uniform ? 0 : reinterpret_cast<uintptr_t>(iCp))) & 15) == 0;
+  return (aligned && nx % 2 == 0) ? tune.vec : 1;
 }
 
 void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
@@ -283,9 +316,7 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   RMA_CHECK_ARG(tune.nontemporal >= 0 && tune.nontemporal <= 3,
                 "nontemporal=" << tune.nontemporal << " (bits 0 and 1)");
   RMA_CHECK_ARG(tune.chunk_z >= 0, "chunk_z=" << tune.chunk_z);
-  const bool aligned = ((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(T2) |
-                         reinterpret_cast<uintptr_t>(iCp)) & 15) == 0;
-  const int V = (aligned && nx % 2 == 0) ? tune.vec : 1;
+  const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
   const int64_t total = plan_boxes(L, boxes, nboxes, V, tune.rows, tune.chunk_z);
   if (L.n == 0) return;
@@ -295,10 +326,10 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   const int remap = tune.xcd_remap ? 1 : 0;
   if (V == 2)
     launch_ru<2>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny, L, c,
-                 remap);
+                 remap, tune.uniform, tune.uniform_value);
   else
     launch_ru<1>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny, L, c,
-                 remap);
+                 remap, tune.uniform, tune.uniform_value);
   RMA_HIP_LAUNCH_CHECK();
 }
 

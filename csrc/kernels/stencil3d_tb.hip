@@ -38,9 +38,14 @@
 // (V, R) = (2, 2) 162 / 3, (2, 4) 230 / 2, (1, 2) 98 / 4, (1, 4) 132 / 3, the same
 // for every non-temporal mask. (2, 4) measured 8-13 % ahead of (2, 2)
 // (profiles/diffusion3d_temporal.md).
+// With Uni (uniform 1/Cp, Stencil3DTuning::uniform: the factor is a kernel
+// argument, no ic registers, no ic shift, no 1/Cp loads, 16 B per cell; the same
+// expression, bitwise the field path; either store setting, no AGPRs, no scratch):
+// (V, R) = (2, 2) 136 / 3, (2, 4) 184 / 2, (1, 2) 90 / 5, (1, 4) 114 / 4.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "rma/hip_check.h"
 #include "rma/kernels.h"
@@ -77,10 +82,14 @@ __device__ __forceinline__ double cell3k(double xl, double c, double xr, double 
   return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
 }
 
-template <int K, int V, int R, bool NTS, bool NTL>
+// 1/Cp as the kernel takes it: the array, or with Uni its one value
+template <bool Uni>
+using Factor = std::conditional_t<Uni, double, const double* __restrict__>;
+
+template <int K, int V, int R, bool NTS, bool NTL, bool Uni = false>
 __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict__ T2,
                                                               const double* __restrict__ T,
-                                                              const double* __restrict__ iCp,
+                                                              Factor<Uni> iCp,
                                                               int64_t nx, int64_t ny, int64_t nz,
                                                               BoxListK L, StencilCoef3 k,
                                                               int remap) {
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
 
   // Lv[l][s][j]: level l, plane slot s (planes p-l-2, p-l-1, p-l when plane p of
   // level 0 is the newest), window row j. ic[l]: 1/Cp of plane p-l-1.
-  double Lv[K][3][NR][V], ic[K][NR][V];
+  double Lv[K][3][NR][V], ic[Uni ? 1 : K][Uni ? 1 : NR][V];
 #pragma unroll
   for (int l = 0; l < K; ++l)
 #pragma unroll
@@ -138,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
 #pragma unroll
       for (int v = 0; v < V; ++v) {
         Lv[l][0][j][v] = Lv[l][1][j][v] = Lv[l][2][j][v] = 0.0;
-        ic[l][j][v] = 0.0;
+        if constexpr (!Uni) ic[l][j][v] = 0.0;
       }
   int64_t p = za - K + 2;
   {
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
     for (int j = 0; j < NR; ++j) load_row<V>(Lv[0][2][j], pf + row[j] + xl);
 #pragma unroll
     for (int j = 1; j < NR - 1; ++j) {
-      load_row<V, NTL>(ic[0][j], iCp + pc * plane + row[j] + xl);
+      if constexpr (!Uni) load_row<V, NTL>(ic[0][j], iCp + pc * plane + row[j] + xl);
       ed[j] = T[pc * plane + row[j] + eidx];
     }
 #pragma unroll
@@ -182,8 +191,10 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
         for (int v = 0; v < V; ++v) {
           const double a = v == 0 ? left : cu[v == 0 ? 0 : v - 1];
           const double c = v == V - 1 ? right : cu[v == V - 1 ? v : v + 1];
-          res[v] = cell3k(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v], Lv[l - 1][2][j][v],
-                          ic[l - 1][j][v], k);
+          double f;
+          if constexpr (Uni) f = iCp; else f = ic[l - 1][j][v];
+          res[v] = cell3k(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v], Lv[l - 1][2][j][v], f,
+                          k);
         }
         if (l < K) {
 #pragma unroll
@@ -203,12 +214,14 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
           Lv[l][0][j][v] = Lv[l][1][j][v];
           Lv[l][1][j][v] = Lv[l][2][j][v];
         }
+    if constexpr (!Uni) {
 #pragma unroll
-    for (int l = K - 1; l > 0; --l)
+      for (int l = K - 1; l > 0; --l)
 #pragma unroll
-      for (int j = 0; j < NR; ++j)
+        for (int j = 0; j < NR; ++j)
 #pragma unroll
-        for (int v = 0; v < V; ++v) ic[l][j][v] = ic[l - 1][j][v];
+          for (int v = 0; v < V; ++v) ic[l][j][v] = ic[l - 1][j][v];
+    }
   }
 }
 
@@ -242,8 +255,17 @@ int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, in
 template <int K, int V, int R>
 void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
                int64_t nx, int64_t ny, int64_t nz, const BoxListK& L, const StencilCoef3& c,
-               int remap) {
+               int remap, bool uni, double fac) {
   const dim3 block(kBlock);
+  if (uni) {  // the 1/Cp-load bit has nothing to act on
+    if (nt & 1)
+      stencil3d_tb_kernel<K, V, R, true, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+                                                                             nz, L, c, remap);
+    else
+      stencil3d_tb_kernel<K, V, R, false, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+                                                                              nz, L, c, remap);
+    return;
+  }
   switch (nt & 3) {
     case 0:
       stencil3d_tb_kernel<K, V, R, false, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
@@ -266,11 +288,15 @@ void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, co
 template <int K>
 void launch_k(int V, int R, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
               const double* iCp, int64_t nx, int64_t ny, int64_t nz, const BoxListK& L,
-              const StencilCoef3& c, int remap) {
-  if (V == 2 && R == 2) launch_nt<K, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
-  else if (V == 2) launch_nt<K, 2, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
-  else if (R == 2) launch_nt<K, 1, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
-  else launch_nt<K, 1, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap);
+              const StencilCoef3& c, int remap, bool uni, double fac) {
+  if (V == 2 && R == 2)
+    launch_nt<K, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+  else if (V == 2)
+    launch_nt<K, 2, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+  else if (R == 2)
+    launch_nt<K, 1, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+  else
+    launch_nt<K, 1, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
 }
 
 }  // namespace
@@ -293,15 +319,13 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
   RMA_CHECK_ARG(tune.tb_nontemporal >= 0 && tune.tb_nontemporal <= 3,
                 "tb_nontemporal=" << tune.tb_nontemporal << " (bits 0 and 1)");
   RMA_CHECK_ARG(tune.tb_chunk_z >= 0, "tb_chunk_z=" << tune.tb_chunk_z);
-  const bool aligned = ((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(T2) |
-                         reinterpret_cast<uintptr_t>(iCp)) & 15) == 0;
-  const int V = (aligned && nx % 2 == 0) ? tune.vec : 1;
+  const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxListK L{};
   const int64_t total = plan_boxes_k(L, boxes, nboxes, K, V, R, tune.tb_chunk_z);
   if (L.n == 0) return;
   RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
   launch_k<2>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal, T2, T, iCp, nx,
-              ny, nz, L, c, tune.xcd_remap ? 1 : 0);
+              ny, nz, L, c, tune.xcd_remap ? 1 : 0, tune.uniform, tune.uniform_value);
   RMA_HIP_LAUNCH_CHECK();
 }
 

@@ -39,7 +39,27 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--check-every", type=int, default=0, help="NaN/Inf guard period")
     ap.add_argument("--temporal", type=int, default=1, choices=[1, 2],
                     help="steps per kernel pass (2: temporal blocking, grid overlap 4, perf only)")
+    ap.add_argument("--no-uniform-factor", dest="uniform_factor", action="store_false",
+                    help="read the 1/Cp array in every pass also where it holds one value")
     return ap
+
+
+def factor_line(model) -> str:
+    """Which 1/Cp path the kernel passes run and its model traffic (rank 0's
+    verdict: the paths are bitwise equal, so ranks need not agree)."""
+    depths = model.uniform_passes()
+    if depths:
+        return (f"[factor] 1/Cp is one value ({model.uniform_value!r}): uniform-factor kernels in "
+                f"the {'/'.join(str(k) for k in depths)}-step passes, 16 B per cell and pass "
+                f"(read T, write T2; the array is not read)")
+    if model.uniform_factor:
+        why = "1/Cp is one value, but only the perf passes on a GPU have the uniform variant"
+    elif not model.cfg.uniform_factor:
+        why = "--no-uniform-factor"
+    else:
+        why = "1/Cp varies, or RMA_DIAG=uniform_factor=off"
+    return (f"[factor] 1/Cp field path, 24 B per cell and pass (read T, read 1/Cp, write T2): "
+            f"{why}")
 
 
 def grid_line(model) -> str | None:
@@ -91,8 +111,11 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     cfg = Diffusion3DConfig(variant=a.variant, nx=a.nx, ny=a.ny, nz=a.nz, nt=a.nt, init=a.init,
                             dims=a.dims, periods=a.periods, transport=a.transport,
-                            device=a.device, check_every=a.check_every, temporal=a.temporal)
+                            device=a.device, check_every=a.check_every, temporal=a.temporal,
+                            uniform_factor=a.uniform_factor)
     model = Diffusion3D(cfg)
+    if model.g.me == 0:
+        print(factor_line(model), flush=True)
     gline = grid_line(model) if a.temporal > 1 else None
     if gline and model.g.me == 0:
         print(gline, flush=True)
@@ -102,6 +125,8 @@ def main(argv=None) -> int:
             print(plan_line(model, res.timed_steps), flush=True)
         res.extra["temporal"] = cfg.temporal
         res.extra["overlaps"] = list(model.g.overlaps)
+    res.extra["uniform_factor"] = model.uniform_factor
+    res.extra["uniform_passes"] = list(model.uniform_passes())
     if a.vis:
         info = visualise(model)
         if info is not None:

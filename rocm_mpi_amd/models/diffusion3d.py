@@ -19,6 +19,17 @@ csrc/kernels/stencil3d_tb.hip): bitwise the same field, half the passes and
 halo exchanges. As in 2D, K-step passes need width-K halos, i.e. grid overlap
 2K, which changes ``nx_g``, ``dx`` and ``dt`` on a multi-rank grid.
 
+Uniform 1/Cp (``uniform_factor``, on by default): the model scans ``iCp`` once
+(``ops.count_differing``, a bit compare with cell 0) and, when every cell holds
+one value, the perf passes on a GPU run the kernels' uniform-factor variants:
+the value travels as a kernel argument, the array is not read, and a pass moves
+16 instead of 24 bytes per cell -- bitwise the same field (the CPU twins always
+read the array). An in-place torch edit of ``iCp`` is seen through the tensor's
+version counter before the next step; after a write torch cannot see (a raw
+pointer, ``ops.fill_``) call ``rescan_factor()``. The verdict is per rank: the
+paths are bitwise equal, so ranks need not agree. ``T_eff`` keeps the
+reference's ``3*nx*ny*nz*8`` bytes per step by definition, whichever path runs.
+
 Out of scope here (the 2D model has them): overlap of the boundary update with
 the interior, passes deeper than two steps, a pass planner and the native
 executor (every pass is issued from Python), checkpointing and direct-store
@@ -26,16 +37,29 @@ halos.
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 
 import torch
 
 from .. import ops
+from ..config import diag_value
 from ..parallel import implicit_grid as gg
 from ..parallel.halo import gather_, update_halo_
 from ..utils import metrics
 
 VARIANTS3D = ("perf", "ap")
+# steps per pass whose uniform-factor kernel the model runs when 1/Cp is one value
+# (profiles/diffusion3d_uniform.md); the others keep the field path
+UNIFORM_PASSES_3D = (1, 2)
+
+
+def _factor_diag_off() -> bool:
+    """RMA_DIAG=uniform_factor=off (the 2D executor's switch)."""
+    v = diag_value("uniform_factor")
+    if v not in ("", "off"):
+        raise ValueError(f"RMA_DIAG uniform_factor={v} (off)")
+    return v == "off"
 
 
 @dataclass
@@ -60,6 +84,7 @@ class Diffusion3DConfig:
     quiet: bool = False
     tuning: ops.Stencil3DTuning | None = None
     temporal: int = 1  # steps per kernel pass (ops.TEMPORAL_3D), perf only
+    uniform_factor: bool = True  # uniform-1/Cp kernel variants where 1/Cp is one value
 
     def validate(self) -> None:
         if self.variant not in VARIANTS3D:
@@ -82,6 +107,7 @@ class Diffusion3D:
 
     def __init__(self, cfg: Diffusion3DConfig, grid_kwargs: dict | None = None):
         cfg.validate()
+        _factor_diag_off()  # a bad value is refused before the grid exists
         self.cfg = cfg
         if not gg.grid_is_initialized():
             kw = dict(grid_kwargs or {})
@@ -116,6 +142,7 @@ class Diffusion3D:
         f64 = dict(dtype=torch.float64, device=self.device)
         self.iCp = torch.empty((nz, ny, nx), **f64)
         ops.fill_(self.iCp, 1.0 / cfg.Cp0)
+        self.rescan_factor()
         self.T = torch.empty((nz, ny, nx), **f64)
         self.init_field(self.T)
         self.T2 = self.T.clone() if cfg.variant == "perf" else None
@@ -158,6 +185,45 @@ class Diffusion3D:
             box += [k if nb[d][0] >= 0 else 1, n[d] - (k if nb[d][1] >= 0 else 1)]
         return tuple(box)
 
+    @property
+    def uniform_factor(self) -> bool:
+        """The verdict of the last scan of 1/Cp: every cell holds one bit pattern
+        (the perf passes on a GPU then do not read the array). False when the
+        config or RMA_DIAG=uniform_factor=off disables the variant."""
+        return self._uniform
+
+    def rescan_factor(self) -> bool:
+        """Examine 1/Cp again (one pass over the array, synchronises) and return
+        the verdict. step() does this by itself after an in-place torch edit;
+        call it after a write torch's version counter does not see."""
+        off = _factor_diag_off()
+        self._iCp_scanned = self.iCp._version
+        self._uniform, self._factor = False, 0.0
+        if self.cfg.uniform_factor and not off and ops.count_differing(self.iCp) == 0:
+            self._uniform, self._factor = True, float(self.iCp[0, 0, 0])
+        return self._uniform
+
+    @property
+    def uniform_value(self) -> float:
+        """The one value of 1/Cp found by the last scan (0.0 without a verdict)."""
+        return self._factor
+
+    def uniform_passes(self) -> tuple:
+        """Steps per pass whose kernel runs its uniform-factor variant now: the
+        perf passes on a GPU, after a scan that found one value."""
+        if not (self._uniform and self.cfg.variant == "perf" and self.device.type == "cuda"):
+            return ()
+        return tuple(k for k in sorted({1, self.cfg.temporal}) if k in UNIFORM_PASSES_3D)
+
+    def _tuning(self, k: int) -> ops.Stencil3DTuning | None:
+        """cfg.tuning, with the uniform-factor variant of a k-step GPU pass on
+        top where the last scan allows it."""
+        tn = self.cfg.tuning
+        if k not in self.uniform_passes():
+            return tn
+        return dataclasses.replace(tn or ops.Stencil3DTuning(), uniform=True,
+                                   uniform_value=self._factor)
+
     def plan(self, n: int) -> list:
         """Passes step(n) runs: n // K passes of K steps, the rest one step each."""
         K = self.cfg.temporal
@@ -165,6 +231,10 @@ class Diffusion3D:
 
     def step(self, n: int = 1) -> None:
         """Advance n time steps (asynchronous on a GPU)."""
+        # uniform-factor passes do not read 1/Cp: an in-place edit since the last
+        # scan must be seen before they run
+        if self.iCp._version != self._iCp_scanned:
+            self.rescan_factor()
         if self.cfg.variant != "perf":
             for _ in range(int(n)):
                 self._step_ap()
@@ -172,10 +242,10 @@ class Diffusion3D:
             return
         for k in self.plan(n):
             if k == 1:
-                ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, tuning=self.cfg.tuning)
+                ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, tuning=self._tuning(1))
             else:
                 ops.stencil3dk_step(k, self.T2, self.T, self.iCp, self.coef, [self.owned_box(k)],
-                                    tuning=self.cfg.tuning)
+                                    tuning=self._tuning(k))
             self.T, self.T2 = self.T2, self.T
             update_halo_(self.T)
             self.steps_done += k

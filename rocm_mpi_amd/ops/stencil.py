@@ -558,6 +558,25 @@ def reduce(A: torch.Tensor, op: str = "sum") -> torch.Tensor:
     return v.min() if op == "min" else v.max()
 
 
+def count_differing(A: torch.Tensor) -> int:
+    """Cells of a contiguous float64 tensor whose 64-bit pattern differs from
+    ``A.flatten()[0]``'s: -0.0 differs from 0.0 and NaNs with another payload
+    count (the uniform-1/Cp verdict: 0 means one value everywhere). One pass
+    (native kernel on the GPU, its CPU twin); synchronises the tensor's stream
+    to read the count."""
+    check_field("A", A)
+    if A.numel() == 0:
+        raise ValueError("count_differing of an empty tensor")
+    if A.is_cuda:
+        out = torch.zeros(2, dtype=torch.int64, device=A.device)
+        native().count_differing(_ptr(A), A.numel(), _ptr(out), stream_handle(A), True)
+        return int(out[0])
+    if _use_native_cpu():
+        return int(native().count_differing(_ptr(A), A.numel(), 0, 0, False))
+    bits = A.reshape(-1).view(torch.int64)
+    return int((bits != bits[0]).sum())
+
+
 def field_stats(A: torch.Tensor) -> tuple[float, float, float]:
     """(non-finite cell count, min, max of the finite cells) of a float64 field
     in ONE pass (native kernel on the GPU and its CPU twin): the full-field

@@ -52,7 +52,15 @@ class Stencil3DTuning:
     and has its own output rows per wave (``tb_rows``: 2, 4), output planes per
     wave task (``tb_chunk_z``) and non-temporal bitmask (``tb_nontemporal``); 0 is
     the measured default of each (4 rows, 32 planes, plain accesses:
-    profiles/diffusion3d_temporal.md)."""
+    profiles/diffusion3d_temporal.md).
+
+    ``uniform``: the caller vouches that every cell of ``iCp`` has the bit pattern
+    of ``uniform_value`` (``Diffusion3D`` decides this with ``ops.count_differing``);
+    both GPU kernels then run their uniform-factor variant, which takes the value
+    as an argument and never reads the array (16 instead of 24 bytes per cell and
+    pass), bitwise equal to the field path. The 1/Cp-load bit (2) of the
+    non-temporal masks has nothing to act on there. CPU tensors accept and ignore both fields: the twins
+    always read the array."""
 
     rows: int = 4
     unroll: int = 2
@@ -63,6 +71,8 @@ class Stencil3DTuning:
     tb_rows: int = 0
     tb_chunk_z: int = 0
     tb_nontemporal: int = 0
+    uniform: bool = False
+    uniform_value: float | None = None  # None: read iCp[0, 0, 0] (synchronises the device)
 
 
 # every (rows, unroll) the launcher instantiates
@@ -140,11 +150,19 @@ def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
+def _uniform_args(tn: Stencil3DTuning, iCp: torch.Tensor) -> tuple[bool, float]:
+    if not tn.uniform:
+        return False, 0.0
+    return True, float(iCp[0, 0, 0]) if tn.uniform_value is None else float(tn.uniform_value)
+
+
 def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: StencilCoef3,
                    boxes: Sequence[Box] | None = None,
                    tuning: Stencil3DTuning | None = None) -> None:
     """One explicit 3D diffusion step on every box (default: the interior):
-    T2[b] = T[b] + dt*iCp*(div q)[b]. Cells outside the boxes keep T2's values."""
+    T2[b] = T[b] + dt*iCp*(div q)[b]. Cells outside the boxes keep T2's values.
+    ``tuning.uniform`` runs the GPU kernel's uniform-factor variant (the array is
+    validated but not read); on CPU tensors it is accepted and ignored."""
     check_field("T", T)
     if T.dim() != 3:
         raise ValueError(f"T must be a (nz, ny, nx) field, got shape {tuple(T.shape)}")
@@ -164,7 +182,8 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
         tn = tuning or Stencil3DTuning()
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  int(tn.rows), int(tn.unroll), int(tn.vec), int(tn.nontemporal),
-                                 int(tn.chunk_z), int(tn.xcd_remap), stream_handle(T), True)
+                                 int(tn.chunk_z), int(tn.xcd_remap), stream_handle(T), True,
+                                 *_uniform_args(tn, iCp))
     elif has_native():
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  4, 1, 2, 0, 0, 0, 0, False)
@@ -178,7 +197,9 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
     """K explicit 3D diffusion steps in one pass: T2[b] = f^K(T)[b] on every box
     (default: the interior), the intermediate levels being f on the interior and
     T on the six faces. Bitwise equal to K full-interior ``stencil3d_step`` calls
-    cropped to the boxes; cells outside the boxes keep T2's values."""
+    cropped to the boxes; cells outside the boxes keep T2's values.
+    ``tuning.uniform`` as in ``stencil3d_step``: the GPU kernel does not read
+    ``iCp`` then; accepted and ignored on CPU tensors."""
     K = int(K)
     if K not in TEMPORAL_3D:
         raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
@@ -206,7 +227,7 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
                                   tuple(coef), int(tn.rows), int(tn.unroll), int(tn.vec),
                                   int(tn.nontemporal), int(tn.chunk_z), int(tn.xcd_remap),
                                   int(tn.tb_rows), int(tn.tb_chunk_z), int(tn.tb_nontemporal),
-                                  stream_handle(T), True)
+                                  stream_handle(T), True, *_uniform_args(tn, iCp))
     elif has_native():
         native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
                                   tuple(coef), 4, 1, 2, 0, 0, 0, 0, 0, 0, 0, False)
