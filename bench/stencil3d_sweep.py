@@ -19,9 +19,17 @@ field-path twin in the same rounds, and reports ``vs_field`` = field median /
 uniform median (profiles/diffusion3d_uniform.md); with ``--temporal 2`` the same
 for the two-step pass. ``spread`` = (max - min) / median over the rounds.
 
+``--fast-math`` times the shipped tuning only (one-step, or with ``--temporal 2``
+the two-step pass next to two one-step launches), each canonical kernel followed
+by its fast7 twin (``Stencil3DTuning.fast_math``; names ending in ``_f7``) in the
+same rounds, and reports ``vs_canonical`` = canonical median / fast7 median
+(profiles/diffusion3d_fastmath.md); with ``--uniform`` the same for the
+uniform-1/Cp variants.
+
     python bench/stencil3d_sweep.py --sizes 512,1024,1536 --ap 1024 --out sweep3d.json
     python bench/stencil3d_sweep.py --temporal 2 --out sweep3d_tb.json
     python bench/stencil3d_sweep.py --uniform --out sweep3d_uni.json
+    python bench/stencil3d_sweep.py --fast-math --uniform --temporal 2 --out sweep3d_f7.json
 """
 from __future__ import annotations
 
@@ -61,39 +69,46 @@ def sweep_size(n: int, a) -> dict:
 
     variants = {}
     steps = {}  # time steps one call of a variant advances (default 1)
+
+    def add(name, fn, tn, nbytes, nsteps=1):
+        """The variant and, with --fast-math, its fast7 twin right after it."""
+        arith = [("", tn)]
+        if a.fast_math:
+            arith.append(("_f7", dataclasses.replace(tn, fast_math=True)))
+        for suffix, t in arith:
+            variants[name + suffix] = ((lambda t=t: fn(t)), nbytes)
+            steps[name + suffix] = nsteps
+
     if a.temporal > 1:
         K = a.temporal
         tunings = []
 
-        def onestep_k():  # K launches of the one-step kernel at its shipped tuning
+        def onestep_k(tn):  # K launches of the one-step kernel at its shipped tuning
             for _ in range(K):
                 dst, src = pair()
-                ops.stencil3d_step(dst, src, iCp, coef)
+                ops.stencil3d_step(dst, src, iCp, coef, tuning=tn)
 
-        variants["onestep_x%d" % K] = (onestep_k, 24.0 * cells * K)
-        steps["onestep_x%d" % K] = K
-        tbs = [ops.Stencil3DTuning(tb_rows=r, tb_chunk_z=cz) for r in ops.TB_ROWS_3D
-               for cz in a.tb_chunk_z]
-        tbs += [ops.Stencil3DTuning(tb_nontemporal=m) for m in (1, 2, 3)]
-        tbs += [ops.Stencil3DTuning(xcd_remap=0)]
+        add("onestep_x%d" % K, onestep_k, ops.Stencil3DTuning(), 24.0 * cells * K, K)
+        if a.fast_math:
+            tbs = [ops.Stencil3DTuning()]
+        else:
+            tbs = [ops.Stencil3DTuning(tb_rows=r, tb_chunk_z=cz) for r in ops.TB_ROWS_3D
+                   for cz in a.tb_chunk_z]
+            tbs += [ops.Stencil3DTuning(tb_nontemporal=m) for m in (1, 2, 3)]
+            tbs += [ops.Stencil3DTuning(xcd_remap=0)]
+
+        def run_tb(tn):
+            dst, src = pair()
+            ops.stencil3dk_step(K, dst, src, iCp, coef, tuning=tn)
+
         for tn in tbs:
             name = (f"tb{K}_r{tn.tb_rows}_cz{tn.tb_chunk_z}_nt{tn.tb_nontemporal}"
                     f"_x{tn.xcd_remap}")
-
-            def run_tb(tn=tn):
-                dst, src = pair()
-                ops.stencil3dk_step(K, dst, src, iCp, coef, tuning=tn)
-
-            variants[name] = (run_tb, 24.0 * cells)
-            steps[name] = K
+            add(name, run_tb, tn, 24.0 * cells, K)
             if a.uniform:
-                def run_tb_uni(tn=dataclasses.replace(tn, uniform=True, uniform_value=1.0)):
-                    dst, src = pair()
-                    ops.stencil3dk_step(K, dst, src, iCp, coef, tuning=tn)
-
-                variants[name + "_uni"] = (run_tb_uni, 16.0 * cells)
-                steps[name + "_uni"] = K
-    elif a.one:
+                add(name + "_uni", run_tb, dataclasses.replace(tn, uniform=True, uniform_value=1.0),
+                    16.0 * cells, K)
+    elif a.one or a.fast_math:
         tunings = [ops.Stencil3DTuning()]
     else:
         tunings = [ops.Stencil3DTuning(rows=r, unroll=u, vec=v, chunk_z=cz)
@@ -104,17 +119,14 @@ def sweep_size(n: int, a) -> dict:
         name = (f"march_r{tn.rows}_u{tn.unroll}_v{tn.vec}_cz{tn.chunk_z}_nt{tn.nontemporal}"
                 f"_x{tn.xcd_remap}")
 
-        def run(tn=tn):
+        def run(tn):
             dst, src = pair()
             ops.stencil3d_step(dst, src, iCp, coef, tuning=tn)
 
-        variants[name] = (run, 24.0 * cells)
+        add(name, run, tn, 24.0 * cells)
         if a.uniform:
-            def run_uni(tn=dataclasses.replace(tn, uniform=True, uniform_value=1.0)):
-                dst, src = pair()
-                ops.stencil3d_step(dst, src, iCp, coef, tuning=tn)
-
-            variants[name + "_uni"] = (run_uni, 16.0 * cells)
+            add(name + "_uni", run, dataclasses.replace(tn, uniform=True, uniform_value=1.0),
+                16.0 * cells)
 
     def triad():
         dst, src = pair()
@@ -154,10 +166,14 @@ def sweep_size(n: int, a) -> dict:
             r["vs_triad"] = tri / r["median_ms"]
             r["vs_copy_rate"] = r["GBps"] / cp
         if k.startswith("tb"):  # > 1: the K-step pass is ahead of K one-step launches
-            r["vs_onestep"] = res["onestep_x%d" % a.temporal]["median_ms"] / r["median_ms"]
+            one = "onestep_x%d" % a.temporal + ("_f7" if k.endswith("_f7") else "")  # same arithmetic
+            r["vs_onestep"] = res[one]["median_ms"] / r["median_ms"]
             r["vs_triad"] = tri / r["median_ms"]  # the ceiling of a 24 B pass is 1
-        if k.endswith("_uni"):  # > 1: the uniform variant is ahead; the traffic model allows 1.5
-            r["vs_field"] = res[k[:-4]]["median_ms"] / r["median_ms"]
+        base = k[:-3] if k.endswith("_f7") else k
+        if base.endswith("_uni"):  # > 1: the uniform variant is ahead; the traffic model allows 1.5
+            r["vs_field"] = res[base[:-4] + k[len(base):]]["median_ms"] / r["median_ms"]
+        if k.endswith("_f7"):  # > 1: fast7 is ahead of the canonical kernel of the same rounds
+            r["vs_canonical"] = res[base]["median_ms"] / r["median_ms"]
     del bufs, iCp
     torch.cuda.empty_cache()
     return res
@@ -196,6 +212,9 @@ def main(argv=None) -> int:
     ap.add_argument("--one", action="store_true", help="default tuning and probes only")
     ap.add_argument("--uniform", action="store_true",
                     help="also the uniform-1/Cp variant of every tuning (vs_field)")
+    ap.add_argument("--fast-math", dest="fast_math", action="store_true",
+                    help="the shipped tuning only, each kernel next to its fast7 twin "
+                         "(vs_canonical)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -211,6 +230,7 @@ def main(argv=None) -> int:
                   + (f"  {r['vs_triad']:.3f} of triad" if "vs_triad" in r else "")
                   + (f"  {r['vs_onestep']:.3f} x one-step" if "vs_onestep" in r else "")
                   + (f"  {r['vs_field']:.3f} x field" if "vs_field" in r else "")
+                  + (f"  {r['vs_canonical']:.3f} x canonical" if "vs_canonical" in r else "")
                   + f"  spread {r['spread']:.3f}",
                   flush=True)
     if a.ap:

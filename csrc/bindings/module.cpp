@@ -213,10 +213,11 @@ PYBIND11_MODULE(_C, m) {
       [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, uintptr_t stream, bool gpu, bool uniform,
-         double uniform_value) {
+         double uniform_value, bool fast_math) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
+          tn.fast_math = fast_math ? 1 : 0;
           tn.uniform = uniform;
           tn.uniform_value = uniform_value;
           tn.rows = rows;
@@ -228,16 +229,22 @@ PYBIND11_MODULE(_C, m) {
           stencil3d_boxes_gpu(P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny, nz,
                               b.data(), (int)b.size(), to_coef3(coef), tn, S(stream));
         } else {
-          py::gil_scoped_release nogil;
-          stencil3d_boxes_cpu(P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny, nz,
-                              b.data(), (int)b.size(), to_coef3(coef));
+          py::gil_scoped_release nogil;  // the CPU twin of the arithmetic
+          if (fast_math)
+            stencil3d7_boxes_cpu(P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny,
+                                 nz, b.data(), (int)b.size(), to_coef3(coef));
+          else
+            stencil3d_boxes_cpu(P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny,
+                                nz, b.data(), (int)b.size(), to_coef3(coef));
         }
       },
       py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
       py::arg("boxes"), py::arg("coef"), py::arg("rows") = 4, py::arg("unroll") = 2,
       py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
       py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true,
-      py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
+      py::arg("uniform") = false, py::arg("uniform_value") = 0.0, py::arg("fast_math") = false);
+  m.def(
+      "fast7_ok", [](const Coef5& coef) { return fast7_ok(to_coef3(coef)); }, py::arg("coef"));
   // cells per lane a GPU launch with these arrays runs (stencil3d_vec)
   m.def(
       "stencil3d_vec",
@@ -256,10 +263,12 @@ PYBIND11_MODULE(_C, m) {
       [](int K, uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
-         int tb_nontemporal, uintptr_t stream, bool gpu, bool uniform, double uniform_value) {
+         int tb_nontemporal, uintptr_t stream, bool gpu, bool uniform, double uniform_value,
+         bool fast_math) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
+          tn.fast_math = fast_math ? 1 : 0;
           tn.uniform = uniform;
           tn.uniform_value = uniform_value;
           tn.rows = rows;
@@ -275,8 +284,12 @@ PYBIND11_MODULE(_C, m) {
                                nz, b.data(), (int)b.size(), to_coef3(coef), tn, S(stream));
         } else {
           py::gil_scoped_release nogil;
-          stencil3dk_boxes_cpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx, ny,
-                               nz, b.data(), (int)b.size(), to_coef3(coef));
+          if (fast_math)
+            stencil3dk7_boxes_cpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx,
+                                  ny, nz, b.data(), (int)b.size(), to_coef3(coef));
+          else
+            stencil3dk_boxes_cpu(K, P<double>(T2), P<const double>(T), P<const double>(iCp), nx,
+                                 ny, nz, b.data(), (int)b.size(), to_coef3(coef));
         }
       },
       py::arg("K"), py::arg("T2"), py::arg("T"), py::arg("iCp"), py::arg("nx"), py::arg("ny"),
@@ -284,7 +297,8 @@ PYBIND11_MODULE(_C, m) {
       py::arg("unroll") = 2, py::arg("vec") = 2, py::arg("nontemporal") = 3,
       py::arg("chunk_z") = 0, py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0,
       py::arg("tb_chunk_z") = 0, py::arg("tb_nontemporal") = 0, py::arg("stream") = 0,
-      py::arg("gpu") = true, py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
+      py::arg("gpu") = true, py::arg("uniform") = false, py::arg("uniform_value") = 0.0,
+      py::arg("fast_math") = false);
   m.def("stencil3dk_has", &stencil3dk_has, py::arg("K"));
   m.def("stencil3dk_has_rows", &stencil3dk_has_rows, py::arg("rows"));
   // Cells of A[0, n) whose bit pattern differs from A[0]'s. GPU: out2 is device

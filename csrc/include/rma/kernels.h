@@ -201,6 +201,10 @@ struct Stencil3DTuning {
   // tb_nontemporal is accepted and has nothing to act on.
   bool uniform = false;
   double uniform_value = 0.0;
+  // 1: the fast7 arithmetic (below) instead of the canonical flux expression,
+  // in both kernels, field and uniform paths. Not bitwise equal to canonical;
+  // needs fast7_ok(coef) (an invalid argument otherwise, before any work).
+  int fast_math = 0;
 };
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
@@ -233,6 +237,32 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
 void stencil3dk_boxes_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
                           int64_t ny, int64_t nz, const Box* boxes, int nboxes,
                           const StencilCoef3& c);
+
+// fast7: the 7-point sum with the constants folded into one per-cell factor
+// (the 3D counterpart of fast5; 8 fp64 operations per update, 7 with uniform
+// 1/Cp, against ~30 of the canonical flux expression). On the host, in double,
+//   ax = (-mlam)*rdx*rdx   ay = (-mlam)*rdy*rdy   az = (-mlam)*rdz*rdz
+//   ry = ay/ax   rz = az/ax   mkc = -2.0*((1.0 + ry) + rz)   gs = dt*ax
+// and per cell, c = T[z][y][x],
+//   sx = T[x+1] + T[x-1]   sy = T[y-1] + T[y+1]   sz = T[z-1] + T[z+1]
+//   t = fma(mkc, c, sx);  t = fma(ry, sy, t);  t = fma(rz, sz, t)
+//   T2 = fma(gs*iCp, t, c)            (gs*iCp is one rounded multiply)
+// With uniform 1/Cp the kernels take g = gs*value, the same product, formed
+// once on the host. Explicit fmas under -ffp-contract=off: the std::fma twins
+// below are bitwise equal to the GPU kernels (Stencil3DTuning::fast_math).
+// fast7_ok: ax != 0 and ay/ax, az/ax and dt*ax finite.
+bool fast7_ok(const StencilCoef3& c);
+struct Fast7 {
+  double mkc, ry, rz, gs;
+};
+Fast7 fast7_constants(const StencilCoef3& c);
+// Same signatures and argument checks as the canonical twins, plus fast7_ok;
+// the K-step twin applies the one-step twin K times through two scratch arrays.
+void stencil3d7_boxes_cpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                          int64_t nz, const Box* boxes, int nboxes, const StencilCoef3& c);
+void stencil3dk7_boxes_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                           int64_t ny, int64_t nz, const Box* boxes, int nboxes,
+                           const StencilCoef3& c);
 
 // Width (in cells) of one wave's x-strip in the march kernel; perf_hide rounds
 // its x-frame so the interior rect starts on a strip boundary.

@@ -132,6 +132,76 @@ void stencil3dk_boxes_cpu(int K, double* T2, const double* T, const double* iCp,
   stencil3d_boxes_cpu(T2, a.data(), iCp, nx, ny, nz, boxes, nboxes, c);
 }
 
+bool fast7_ok(const StencilCoef3& c) {
+  const double ax = (-c.mlam) * c.rdx * c.rdx, ay = (-c.mlam) * c.rdy * c.rdy,
+               az = (-c.mlam) * c.rdz * c.rdz;
+  return ax != 0.0 && std::isfinite(ax) && std::isfinite(ay) && std::isfinite(az) &&
+         std::isfinite(ay / ax) && std::isfinite(az / ax) && std::isfinite(c.dt * ax);
+}
+
+Fast7 fast7_constants(const StencilCoef3& c) {
+  const double ax = (-c.mlam) * c.rdx * c.rdx;
+  const double ay = (-c.mlam) * c.rdy * c.rdy;
+  const double az = (-c.mlam) * c.rdz * c.rdz;
+  Fast7 f;
+  f.ry = ay / ax;
+  f.rz = az / ax;
+  f.mkc = -2.0 * ((1.0 + f.ry) + f.rz);
+  f.gs = c.dt * ax;
+  return f;
+}
+
+// fast7 arithmetic (rma/kernels.h): the 7-point sum with one folded per-cell
+// factor. std::fma rounds once like v_fma_f64, so this twin is bitwise equal to
+// the fast7 instantiations of stencil3d.hip / stencil3d_tb.hip
+// (tests/test_stencil3d_fast_cpu.py pins it to an exact-rational model).
+void stencil3d7_boxes_cpu(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                          int64_t nz, const Box* boxes, int nboxes, const StencilCoef3& k) {
+  validate_boxes(T2, T, nx, ny, nz, boxes, nboxes);
+  RMA_CHECK_ARG(fast7_ok(k), "fast7 needs lam != 0 and finite coefficients");
+  const Fast7 f = fast7_constants(k);
+  const int64_t plane = nx * ny;
+  for (int i = 0; i < nboxes; ++i) {
+    const Box b = boxes[i];
+    if (b.empty()) continue;
+    const int64_t rows = b.y1 - b.y0;
+    parallel_for(0, rows * (b.z1 - b.z0), 64, [&](int64_t j) {
+      const int64_t o = (b.z0 + j / rows) * plane + (b.y0 + j % rows) * nx;
+      const double* cu = T + o;
+      for (int64_t x = b.x0; x < b.x1; ++x) {
+        const double c = cu[x];
+        const double g = f.gs * iCp[o + x];
+        const double sx = cu[x + 1] + cu[x - 1];
+        const double sy = cu[x - nx] + cu[x + nx];
+        const double sz = cu[x - plane] + cu[x + plane];
+        double t = std::fma(f.mkc, c, sx);
+        t = std::fma(f.ry, sy, t);
+        t = std::fma(f.rz, sz, t);
+        T2[o + x] = std::fma(g, t, c);
+      }
+    });
+  }
+}
+
+void stencil3dk7_boxes_cpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                           int64_t ny, int64_t nz, const Box* boxes, int nboxes,
+                           const StencilCoef3& c) {
+  RMA_CHECK_ARG(K >= 1, "K=" << K);
+  validate_boxes(T2, T, nx, ny, nz, boxes, nboxes);
+  RMA_CHECK_ARG(fast7_ok(c), "fast7 needs lam != 0 and finite coefficients");
+  if (K == 1) {
+    stencil3d7_boxes_cpu(T2, T, iCp, nx, ny, nz, boxes, nboxes, c);
+    return;
+  }
+  std::vector<double> a(T, T + nx * ny * nz), b(a);
+  const Box interior{1, nx - 1, 1, ny - 1, 1, nz - 1};
+  for (int j = 1; j < K; ++j) {  // levels 1..K-1 on the interior, T on the faces
+    stencil3d7_boxes_cpu(b.data(), a.data(), iCp, nx, ny, nz, &interior, 1, c);
+    a.swap(b);
+  }
+  stencil3d7_boxes_cpu(T2, a.data(), iCp, nx, ny, nz, boxes, nboxes, c);
+}
+
 bool fast5_ok(const StencilCoef& c) {
   const double ax = (-c.mlam) * c.rdx * c.rdx, ay = (-c.mlam) * c.rdy * c.rdy;
   return ax != 0.0 && std::isfinite(ax) && std::isfinite(ay) && std::isfinite(ay / ax) &&

@@ -32,6 +32,13 @@
 //     kernel argument, the array is never dereferenced and no ic registers are
 //     held: 16 B/cell. The same expression in the same order, so bitwise the
 //     field path's result. Bit 1 of nontemporal has nothing to act on there.
+//   * fast7 (Stencil3DTuning::fast_math, template parameter A = kFast7; rma/kernels.h):
+//     the 7-point sum with the folded constants as the kernel argument, explicit
+//     fmas, no flux temporaries: bitwise equal to stencil3d7_boxes_cpu, rounding-
+//     close to canonical. The field path keeps ic and multiplies by gs at use; Uni
+//     takes g = gs * value. Same loads, stores and masks in both arithmetics, the
+//     thin-box path included. HBM-bound either way: no faster than canonical
+//     (profiles/diffusion3d_fastmath.md).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,7 +74,16 @@ __device__ __forceinline__ double cell3(double xl, double c, double xr, double u
   return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
 }
 
-// 1/Cp as the kernels take it: the array, or with Uni its one value
+// the update of one cell in arithmetic A (f: 1/Cp of the cell, or what Factor<true> holds)
+template <int A, bool Uni>
+__device__ __forceinline__ double update3(double xl, double c, double xr, double up, double dn,
+                                          double bk, double fr, double f, const Coef3<A>& k) {
+  if constexpr (A == kFast7) return cell7<Uni>(xl, c, xr, up, dn, bk, fr, f, k);
+  else return cell3(xl, c, xr, up, dn, bk, fr, f, k);
+}
+
+// 1/Cp as the kernels take it: the array, or with Uni its one value (fast7: gs
+// times that value)
 template <bool Uni>
 using Factor = std::conditional_t<Uni, double, const double* __restrict__>;
 
@@ -86,10 +102,10 @@ struct Task {
 
 // UU planes z .. z+UU-1: P[0] / P[1] hold the own rows of planes z-1 / z on
 // entry and of planes z+UU-1 / z+UU on exit.
-template <int V, int R, int UU, int NP, bool NTS, bool NTL, bool Uni>
+template <int V, int R, int UU, int NP, bool NTS, bool NTL, bool Uni, int A>
 __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restrict__ T2,
                                         const double* __restrict__ T, Factor<Uni> iCp,
-                                        const Task<V, R>& t, int64_t z, const StencilCoef3& k) {
+                                        const Task<V, R>& t, int64_t z, const Coef3<A>& k) {
   static_assert(UU + 2 <= NP, "plane registers");
   double H[UU][2][V], ic[Uni ? 1 : UU][Uni ? 1 : R][V], ed[UU][R];
 #pragma unroll
@@ -123,7 +139,7 @@ __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restric
         const double xr = v == V - 1 ? right : cu[v == V - 1 ? v : v + 1];
         double f;
         if constexpr (Uni) f = iCp; else f = ic[u][r][v];
-        res[v] = cell3(xl, cu[v], xr, up[v], dn[v], P[u][r][v], P[u + 2][r][v], f, k);
+        res[v] = update3<A, Uni>(xl, cu[v], xr, up[v], dn[v], P[u][r][v], P[u + 2][r][v], f, k);
       }
       if (r < t.nrows) store_row<V, NTS>(T2 + (z + u) * t.plane + t.row[r] + t.x, res, t.m);
     }
@@ -144,12 +160,17 @@ __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restric
 // With Uni (either store setting; no AGPRs, no scratch): V = 2 (2, 1) 70 / 7, (2, 2) 115 / 4,
 // (4, 1) 110 / 4, (4, 2) 179 / 2, (8, 1) 191 / 2; V = 1 (2, 1) 52 / 8, (2, 2) 88 / 5,
 // (4, 1) 70 / 7, (4, 2) 137 / 3, (8, 1) 135 / 3.
-template <int V, int R, int U, bool NTS, bool NTL, bool Uni = false>
+// fast7 (no AGPRs, no scratch), field: V = 2 (2, 1) 74 / 6, (2, 2) 129 / 3, (4, 1) 126 / 4,
+// (4, 2) 217 / 2, (8, 1) 231 / 2; V = 1 (2, 1) 54 / 8, (2, 2) 96 / 5, (4, 1) 88 / 5, (4, 2) 161 / 3,
+// (8, 1) 161 / 3. fast7 with Uni: V = 2 (2, 1) 62 / 8, (2, 2) 104 / 4, (4, 1) 102 / 4,
+// (4, 2) 169 / 2, (8, 1) 183 / 2; V = 1 (2, 1) 50 / 8, (2, 2) 80 / 6, (4, 1) 70 / 7, (4, 2) 129 / 3,
+// (8, 1) 126-127 / 4.
+template <int V, int R, int U, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3>
 __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restrict__ T2,
                                                                  const double* __restrict__ T,
                                                                  Factor<Uni> iCp,
                                                                  int64_t nx, int64_t ny,
-                                                                 BoxList L, StencilCoef3 k,
+                                                                 BoxList L, Coef3<A> k,
                                                                  int remap) {
   const int64_t b = remap ? xcd_remap(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -169,8 +190,8 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
     for (int64_t x = box.x0; x < box.x1; ++x) {
       double f;
       if constexpr (Uni) f = iCp; else f = iCp[o + x];
-      const double v = cell3(T[o + x - 1], T[o + x], T[o + x + 1], T[o - nx + x], T[o + nx + x],
-                             T[o - plane + x], T[o + plane + x], f, k);
+      const double v = update3<A, Uni>(T[o + x - 1], T[o + x], T[o + x + 1], T[o - nx + x],
+                                       T[o + nx + x], T[o - plane + x], T[o + plane + x], f, k);
       if constexpr (NTS) {
         __builtin_nontemporal_store(v, T2 + o + x);
       } else {
@@ -211,9 +232,9 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
     load_row<V>(P[1][r], T + za * plane + t.row[r] + t.xl);
   }
   int64_t z = za;
-  for (; z + U <= zb; z += U) z_steps<V, R, U, U + 2, NTS, NTL, Uni>(P, T2, T, iCp, t, z, k);
+  for (; z + U <= zb; z += U) z_steps<V, R, U, U + 2, NTS, NTL, Uni, A>(P, T2, T, iCp, t, z, k);
   if constexpr (U > 1) {
-    for (; z < zb; ++z) z_steps<V, R, 1, U + 2, NTS, NTL, Uni>(P, T2, T, iCp, t, z, k);
+    for (; z < zb; ++z) z_steps<V, R, 1, U + 2, NTS, NTL, Uni, A>(P, T2, T, iCp, t, z, k);
   }
 }
 
@@ -247,48 +268,48 @@ int64_t plan_boxes(BoxList& L, const Box* boxes, int nboxes, int V, int R, int c
   return total;
 }
 
-template <int V, int R, int U>
+template <int V, int R, int U, int A>
 void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-               int64_t nx, int64_t ny, const BoxList& L, const StencilCoef3& c, int remap,
+               int64_t nx, int64_t ny, const BoxList& L, const Coef3<A>& c, int remap,
                bool uni, double fac) {
   const dim3 block(kBlock);
   if (uni) {  // the 1/Cp-load bit has nothing to act on
     if (nt & 1)
-      stencil3d_march_kernel<V, R, U, true, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+      stencil3d_march_kernel<V, R, U, true, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
                                                                                 L, c, remap);
     else
-      stencil3d_march_kernel<V, R, U, false, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx,
+      stencil3d_march_kernel<V, R, U, false, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx,
                                                                                  ny, L, c, remap);
     return;
   }
   switch (nt & 3) {
     case 0:
-      stencil3d_march_kernel<V, R, U, false, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
+      stencil3d_march_kernel<V, R, U, false, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
                                                                            c, remap);
       break;
     case 1:
-      stencil3d_march_kernel<V, R, U, true, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
+      stencil3d_march_kernel<V, R, U, true, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
                                                                           c, remap);
       break;
     case 2:
-      stencil3d_march_kernel<V, R, U, false, true><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
+      stencil3d_march_kernel<V, R, U, false, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
                                                                           c, remap);
       break;
     default:
-      stencil3d_march_kernel<V, R, U, true, true><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
+      stencil3d_march_kernel<V, R, U, true, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
                                                                          c, remap);
   }
 }
 
-template <int V>
+template <int V, int A>
 void launch_ru(int R, int U, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
                const double* iCp, int64_t nx, int64_t ny, const BoxList& L,
-               const StencilCoef3& c, int remap, bool uni, double fac) {
-  if (R == 2 && U == 1) launch_nt<V, 2, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else if (R == 2) launch_nt<V, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else if (R == 4 && U == 1) launch_nt<V, 4, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else if (R == 4) launch_nt<V, 4, 2>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else launch_nt<V, 8, 1>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+               const Coef3<A>& c, int remap, bool uni, double fac) {
+  if (R == 2 && U == 1) launch_nt<V, 2, 1, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else if (R == 2) launch_nt<V, 2, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else if (R == 4 && U == 1) launch_nt<V, 4, 1, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else if (R == 4) launch_nt<V, 4, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
+  else launch_nt<V, 8, 1, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
 }
 
 }  // namespace
@@ -316,6 +337,8 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   RMA_CHECK_ARG(tune.nontemporal >= 0 && tune.nontemporal <= 3,
                 "nontemporal=" << tune.nontemporal << " (bits 0 and 1)");
   RMA_CHECK_ARG(tune.chunk_z >= 0, "chunk_z=" << tune.chunk_z);
+  RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
+                "fast_math: fast7 needs lam != 0 and finite coefficients");
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
   const int64_t total = plan_boxes(L, boxes, nboxes, V, tune.rows, tune.chunk_z);
@@ -324,12 +347,22 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   const dim3 grid((unsigned)total);
   hipStream_t s = as_stream(stream);
   const int remap = tune.xcd_remap ? 1 : 0;
-  if (V == 2)
-    launch_ru<2>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny, L, c,
-                 remap, tune.uniform, tune.uniform_value);
-  else
-    launch_ru<1>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny, L, c,
-                 remap, tune.uniform, tune.uniform_value);
+  if (tune.fast_math) {  // the uniform variant takes g = gs * value, formed here
+    const Fast7 f = fast7_constants(c);
+    const double g = f.gs * tune.uniform_value;
+    if (V == 2)
+      launch_ru<2, kFast7>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny,
+                           L, f, remap, tune.uniform, g);
+    else
+      launch_ru<1, kFast7>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny,
+                           L, f, remap, tune.uniform, g);
+  } else if (V == 2) {
+    launch_ru<2, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
+                              ny, L, c, remap, tune.uniform, tune.uniform_value);
+  } else {
+    launch_ru<1, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
+                              ny, L, c, remap, tune.uniform, tune.uniform_value);
+  }
   RMA_HIP_LAUNCH_CHECK();
 }
 

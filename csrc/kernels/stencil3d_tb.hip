@@ -42,6 +42,14 @@
 // argument, no ic registers, no ic shift, no 1/Cp loads, 16 B per cell; the same
 // expression, bitwise the field path; either store setting, no AGPRs, no scratch):
 // (V, R) = (2, 2) 136 / 3, (2, 4) 184 / 2, (1, 2) 90 / 5, (1, 4) 114 / 4.
+// fast7 (Stencil3DTuning::fast_math, template parameter A = kFast7; rma/kernels.h: the
+// 7-point sum with the folded constants as the kernel argument, explicit fmas, no flux
+// temporaries; the field path keeps ic and multiplies by gs at use, Uni takes
+// g = gs * value; bitwise equal to stencil3dk7_boxes_cpu; no AGPRs, no scratch):
+// (V, R) = (2, 2) 154 / 3, (2, 4) 222 / 2, (1, 2) 94 / 5, (1, 4) 128 / 4; with Uni
+// (2, 2) 126 / 4, (2, 4) 180 / 2, (1, 2) 82 / 5, (1, 4) 102 / 4. (2, 4) stays at 2 waves
+// (3 need 168 or fewer). Same-run against canonical: 1.01-1.06x on the field path,
+// 1.15-1.24x with Uni (profiles/diffusion3d_fastmath.md).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -82,16 +90,25 @@ __device__ __forceinline__ double cell3k(double xl, double c, double xr, double 
   return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
 }
 
-// 1/Cp as the kernel takes it: the array, or with Uni its one value
+// the update of one cell in arithmetic A (f: 1/Cp of the cell, or what Factor<true> holds)
+template <int A, bool Uni>
+__device__ __forceinline__ double update3k(double xl, double c, double xr, double up, double dn,
+                                           double bk, double fr, double f, const Coef3<A>& k) {
+  if constexpr (A == kFast7) return cell7<Uni>(xl, c, xr, up, dn, bk, fr, f, k);
+  else return cell3k(xl, c, xr, up, dn, bk, fr, f, k);
+}
+
+// 1/Cp as the kernel takes it: the array, or with Uni its one value (fast7: gs
+// times that value)
 template <bool Uni>
 using Factor = std::conditional_t<Uni, double, const double* __restrict__>;
 
-template <int K, int V, int R, bool NTS, bool NTL, bool Uni = false>
+template <int K, int V, int R, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3>
 __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict__ T2,
                                                               const double* __restrict__ T,
                                                               Factor<Uni> iCp,
                                                               int64_t nx, int64_t ny, int64_t nz,
-                                                              BoxListK L, StencilCoef3 k,
+                                                              BoxListK L, Coef3<A> k,
                                                               int remap) {
   constexpr int NR = R + 2 * K;                 // rows of the level-0 window
   constexpr int64_t kStep = kWave * V - 2 * (K - 1);  // strip advance
@@ -193,8 +210,8 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
           const double c = v == V - 1 ? right : cu[v == V - 1 ? v : v + 1];
           double f;
           if constexpr (Uni) f = iCp; else f = ic[l - 1][j][v];
-          res[v] = cell3k(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v], Lv[l - 1][2][j][v], f,
-                          k);
+          res[v] = update3k<A, Uni>(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v],
+                                    Lv[l - 1][2][j][v], f, k);
         }
         if (l < K) {
 #pragma unroll
@@ -252,51 +269,51 @@ int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, in
   return total;
 }
 
-template <int K, int V, int R>
+template <int K, int V, int R, int A>
 void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-               int64_t nx, int64_t ny, int64_t nz, const BoxListK& L, const StencilCoef3& c,
+               int64_t nx, int64_t ny, int64_t nz, const BoxListK& L, const Coef3<A>& c,
                int remap, bool uni, double fac) {
   const dim3 block(kBlock);
   if (uni) {  // the 1/Cp-load bit has nothing to act on
     if (nt & 1)
-      stencil3d_tb_kernel<K, V, R, true, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+      stencil3d_tb_kernel<K, V, R, true, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
                                                                              nz, L, c, remap);
     else
-      stencil3d_tb_kernel<K, V, R, false, false, true><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+      stencil3d_tb_kernel<K, V, R, false, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
                                                                               nz, L, c, remap);
     return;
   }
   switch (nt & 3) {
     case 0:
-      stencil3d_tb_kernel<K, V, R, false, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+      stencil3d_tb_kernel<K, V, R, false, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
                                                                         c, remap);
       break;
     case 1:
-      stencil3d_tb_kernel<K, V, R, true, false><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+      stencil3d_tb_kernel<K, V, R, true, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
                                                                        c, remap);
       break;
     case 2:
-      stencil3d_tb_kernel<K, V, R, false, true><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+      stencil3d_tb_kernel<K, V, R, false, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
                                                                        c, remap);
       break;
     default:
-      stencil3d_tb_kernel<K, V, R, true, true><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
+      stencil3d_tb_kernel<K, V, R, true, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
                                                                       c, remap);
   }
 }
 
-template <int K>
+template <int K, int A>
 void launch_k(int V, int R, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
               const double* iCp, int64_t nx, int64_t ny, int64_t nz, const BoxListK& L,
-              const StencilCoef3& c, int remap, bool uni, double fac) {
+              const Coef3<A>& c, int remap, bool uni, double fac) {
   if (V == 2 && R == 2)
-    launch_nt<K, 2, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+    launch_nt<K, 2, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
   else if (V == 2)
-    launch_nt<K, 2, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+    launch_nt<K, 2, 4, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
   else if (R == 2)
-    launch_nt<K, 1, 2>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+    launch_nt<K, 1, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
   else
-    launch_nt<K, 1, 4>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
+    launch_nt<K, 1, 4, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
 }
 
 }  // namespace
@@ -319,13 +336,23 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
   RMA_CHECK_ARG(tune.tb_nontemporal >= 0 && tune.tb_nontemporal <= 3,
                 "tb_nontemporal=" << tune.tb_nontemporal << " (bits 0 and 1)");
   RMA_CHECK_ARG(tune.tb_chunk_z >= 0, "tb_chunk_z=" << tune.tb_chunk_z);
+  RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
+                "fast_math: fast7 needs lam != 0 and finite coefficients");
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxListK L{};
   const int64_t total = plan_boxes_k(L, boxes, nboxes, K, V, R, tune.tb_chunk_z);
   if (L.n == 0) return;
   RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
-  launch_k<2>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal, T2, T, iCp, nx,
-              ny, nz, L, c, tune.xcd_remap ? 1 : 0, tune.uniform, tune.uniform_value);
+  if (tune.fast_math) {  // the uniform variant takes g = gs * value, formed here
+    const Fast7 f = fast7_constants(c);
+    launch_k<2, kFast7>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal, T2, T,
+                        iCp, nx, ny, nz, L, f, tune.xcd_remap ? 1 : 0, tune.uniform,
+                        f.gs * tune.uniform_value);
+  } else {
+    launch_k<2, kCanonical3>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal,
+                             T2, T, iCp, nx, ny, nz, L, c, tune.xcd_remap ? 1 : 0, tune.uniform,
+                             tune.uniform_value);
+  }
   RMA_HIP_LAUNCH_CHECK();
 }
 

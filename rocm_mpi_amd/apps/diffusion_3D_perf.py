@@ -41,6 +41,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="steps per kernel pass (2: temporal blocking, grid overlap 4, perf only)")
     ap.add_argument("--no-uniform-factor", dest="uniform_factor", action="store_false",
                     help="read the 1/Cp array in every pass also where it holds one value")
+    ap.add_argument("--fast-math", dest="fast_math", action="store_true",
+                    help="every pass in the fast7 arithmetic (7-point sum, one folded per-cell "
+                         "factor; rounding-level difference from canonical, perf only)")
     return ap
 
 
@@ -88,8 +91,10 @@ def plan_line(model, steps: int) -> str:
     plan = model.plan(steps)
     passes = ", ".join(f"{n} x {k}" for k, n in sorted(collections.Counter(plan).items(),
                                                          reverse=True))
-    return (f"[plan] {steps} timed steps in passes of {passes} step(s); canonical (bitwise = "
-            f"one-step updates); max {model.cfg.temporal} steps per pass (--temporal)")
+    arith = ("fast-math (fast7: 7-point sum, folded factor; rounding-level vs canonical)"
+             if model.cfg.fast_math else "canonical (bitwise = one-step updates)")
+    return (f"[plan] {steps} timed steps in passes of {passes} step(s); {arith}; max "
+            f"{model.cfg.temporal} steps per pass (--temporal)")
 
 
 def visualise(model, outdir: str = "output") -> dict | None:
@@ -112,7 +117,7 @@ def main(argv=None) -> int:
     cfg = Diffusion3DConfig(variant=a.variant, nx=a.nx, ny=a.ny, nz=a.nz, nt=a.nt, init=a.init,
                             dims=a.dims, periods=a.periods, transport=a.transport,
                             device=a.device, check_every=a.check_every, temporal=a.temporal,
-                            uniform_factor=a.uniform_factor)
+                            uniform_factor=a.uniform_factor, fast_math=a.fast_math)
     model = Diffusion3D(cfg)
     if model.g.me == 0:
         print(factor_line(model), flush=True)
@@ -120,9 +125,9 @@ def main(argv=None) -> int:
     if gline and model.g.me == 0:
         print(gline, flush=True)
     res = model.run()
+    if (a.temporal > 1 or a.fast_math) and model.g.me == 0:
+        print(plan_line(model, res.timed_steps), flush=True)
     if a.temporal > 1:
-        if model.g.me == 0:
-            print(plan_line(model, res.timed_steps), flush=True)
         res.extra["temporal"] = cfg.temporal
         res.extra["overlaps"] = list(model.g.overlaps)
     res.extra["uniform_factor"] = model.uniform_factor

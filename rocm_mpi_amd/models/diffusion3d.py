@@ -30,6 +30,15 @@ pointer, ``ops.fill_``) call ``rescan_factor()``. The verdict is per rank: the
 paths are bitwise equal, so ranks need not agree. ``T_eff`` keeps the
 reference's ``3*nx*ny*nz*8`` bytes per step by definition, whichever path runs.
 
+``fast_math`` (perf only, off by default): every pass of ``plan(n)``, the
+one-step remainder passes included, runs the fast7 arithmetic (``ops.fast7_ok``;
+the 7-point sum with the constants folded into one per-cell factor, 8 fp64
+operations per update instead of about 30). The field is then independent of
+the plan, of the decomposition, of the uniform-factor path and of the device
+(the C++ twin is bitwise equal to the kernels), and rounding-close to the
+canonical field, not bitwise equal to it. It combines with ``temporal`` and with
+the uniform-factor scan unchanged.
+
 Out of scope here (the 2D model has them): overlap of the boundary update with
 the interior, passes deeper than two steps, a pass planner and the native
 executor (every pass is issued from Python), checkpointing and direct-store
@@ -85,6 +94,7 @@ class Diffusion3DConfig:
     tuning: ops.Stencil3DTuning | None = None
     temporal: int = 1  # steps per kernel pass (ops.TEMPORAL_3D), perf only
     uniform_factor: bool = True  # uniform-1/Cp kernel variants where 1/Cp is one value
+    fast_math: bool = False  # the fast7 arithmetic in every pass, perf only
 
     def validate(self) -> None:
         if self.variant not in VARIANTS3D:
@@ -99,6 +109,8 @@ class Diffusion3DConfig:
             raise ValueError(f"temporal must be one of {ops.TEMPORAL_3D}")
         if self.temporal > 1 and self.variant != "perf":
             raise ValueError("temporal blocking applies to the perf variant")
+        if self.fast_math and self.variant != "perf":
+            raise ValueError("fast_math applies to the perf variant")
 
 
 class Diffusion3D:
@@ -139,6 +151,10 @@ class Diffusion3D:
         self.dt = min(self.dx * self.dx, self.dy * self.dy, self.dz * self.dz) \
             * cfg.Cp0 / cfg.lam / 6.1
         self.coef = ops.StencilCoef3.from_physics(cfg.lam, self.dx, self.dy, self.dz, self.dt)
+        if cfg.fast_math and not ops.fast7_ok(self.coef):
+            self.close()
+            raise ValueError("fast_math: the fast7 arithmetic needs lam != 0 and finite "
+                             f"coefficients, got {tuple(self.coef)}")
         f64 = dict(dtype=torch.float64, device=self.device)
         self.iCp = torch.empty((nz, ny, nx), **f64)
         ops.fill_(self.iCp, 1.0 / cfg.Cp0)
@@ -216,9 +232,11 @@ class Diffusion3D:
         return tuple(k for k in sorted({1, self.cfg.temporal}) if k in UNIFORM_PASSES_3D)
 
     def _tuning(self, k: int) -> ops.Stencil3DTuning | None:
-        """cfg.tuning, with the uniform-factor variant of a k-step GPU pass on
-        top where the last scan allows it."""
+        """cfg.tuning, with cfg.fast_math and the uniform-factor variant of a
+        k-step GPU pass on top where the last scan allows it."""
         tn = self.cfg.tuning
+        if self.cfg.fast_math:
+            tn = dataclasses.replace(tn or ops.Stencil3DTuning(), fast_math=True)
         if k not in self.uniform_passes():
             return tn
         return dataclasses.replace(tn or ops.Stencil3DTuning(), uniform=True,
@@ -315,6 +333,7 @@ class Diffusion3D:
             transport=g.transport, device=str(self.device))
         res.extra["nz"] = cfg.nz
         res.extra["nzg"] = g.nxyz_g[2]
+        res.extra["fast_math"] = bool(cfg.fast_math)
         if g.me == 0 and not cfg.quiet:
             print(metrics.reference_line(nt, wtime, teff), flush=True)
         return res

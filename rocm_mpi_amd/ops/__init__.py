@@ -7,7 +7,7 @@ from .stencil import (FAST5, KERNELS, KSTEP_CORE, LAB_KERNELS, PIPE, PIPE_MAX_K,
                       validate_rects)
 from .stencil3d import (TB_ROWS_3D, TEMPORAL_3D, TUNINGS_3D, Box, Stencil3DTuning, StencilCoef3,
                         TileGeometry3, init_gaussian3d_, init_random3d_, interior_box,
-                        stencil3d_step, stencil3d_torch, stencil3dk_step, stencil3dk_torch,
+                        fast7_ok, stencil3d_step, stencil3d_torch, stencil3dk_step, stencil3dk_torch,
                         validate_boxes)
 from .halo_ops import copy_plane, copy_planes
 from .block_ops import assemble_blocks, copy_blocks
@@ -21,5 +21,5 @@ __all__ = [
     "assemble_blocks", "copy_blocks",
     "TUNINGS_3D", "Box", "Stencil3DTuning", "StencilCoef3", "TileGeometry3", "init_gaussian3d_",
     "init_random3d_", "interior_box", "stencil3d_step", "stencil3d_torch", "validate_boxes",
-    "TB_ROWS_3D", "TEMPORAL_3D", "stencil3dk_step", "stencil3dk_torch",
+    "TB_ROWS_3D", "TEMPORAL_3D", "fast7_ok", "stencil3dk_step", "stencil3dk_torch",
 ]

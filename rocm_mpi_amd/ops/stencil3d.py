@@ -14,6 +14,7 @@ the 2D expression with the z flux difference subtracted last::
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Iterable, NamedTuple, Sequence
 
@@ -60,7 +61,14 @@ class Stencil3DTuning:
     as an argument and never reads the array (16 instead of 24 bytes per cell and
     pass), bitwise equal to the field path. The 1/Cp-load bit (2) of the
     non-temporal masks has nothing to act on there. CPU tensors accept and ignore both fields: the twins
-    always read the array."""
+    always read the array.
+
+    ``fast_math``: the fast7 arithmetic (``fast7_ok``; the 7-point sum with the
+    constants folded into one per-cell factor, 8 fp64 operations per update instead
+    of about 30) in both kernels, field and uniform paths alike. Rounding-close to
+    the canonical update, not bitwise equal to it. CPU tensors honour it: they run
+    the fast7 C++ twin, bitwise equal to the GPU kernels. It needs the native
+    extension and a coefficient set that passes ``fast7_ok``."""
 
     rows: int = 4
     unroll: int = 2
@@ -73,6 +81,7 @@ class Stencil3DTuning:
     tb_nontemporal: int = 0
     uniform: bool = False
     uniform_value: float | None = None  # None: read iCp[0, 0, 0] (synchronises the device)
+    fast_math: bool = False
 
 
 # every (rows, unroll) the launcher instantiates
@@ -150,6 +159,29 @@ def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
+def fast7_ok(coef: StencilCoef3) -> bool:
+    """Mirror of rma::fast7_ok: fast7 divides by lam/dx^2, so it needs lam != 0
+    and finite folded constants (ay/ax, az/ax, dt*ax)."""
+    c = StencilCoef3(*coef)
+    ax, ay, az = ((-c.mlam) * r * r for r in (c.rdx, c.rdy, c.rdz))
+    if ax == 0.0 or not all(math.isfinite(v) for v in (ax, ay, az)):
+        return False
+    return all(math.isfinite(v) for v in (ay / ax, az / ax, c.dt * ax))
+
+
+def _fast_math(tn: "Stencil3DTuning | None", coef: StencilCoef3) -> bool:
+    """tuning.fast_math, refused before any work where it cannot run."""
+    if tn is None or not tn.fast_math:
+        return False
+    if not fast7_ok(coef):
+        raise ValueError("fast_math: the fast7 arithmetic needs lam != 0 and finite "
+                         f"coefficients, got {tuple(coef)}")
+    if not has_native():
+        raise RuntimeError("fast_math needs the native extension (python -m rocm_mpi_amd._build): "
+                           "there is no torch formulation of the fast7 arithmetic")
+    return True
+
+
 def _uniform_args(tn: Stencil3DTuning, iCp: torch.Tensor) -> tuple[bool, float]:
     if not tn.uniform:
         return False, 0.0
@@ -162,7 +194,8 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
     """One explicit 3D diffusion step on every box (default: the interior):
     T2[b] = T[b] + dt*iCp*(div q)[b]. Cells outside the boxes keep T2's values.
     ``tuning.uniform`` runs the GPU kernel's uniform-factor variant (the array is
-    validated but not read); on CPU tensors it is accepted and ignored."""
+    validated but not read); on CPU tensors it is accepted and ignored.
+    ``tuning.fast_math`` runs the fast7 arithmetic, on GPU and CPU tensors alike."""
     check_field("T", T)
     if T.dim() != 3:
         raise ValueError(f"T must be a (nz, ny, nx) field, got shape {tuple(T.shape)}")
@@ -178,15 +211,16 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
     if not boxes:
         return
     coef = StencilCoef3(*coef)
+    fast = _fast_math(tuning, coef)
     if T.is_cuda:
         tn = tuning or Stencil3DTuning()
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  int(tn.rows), int(tn.unroll), int(tn.vec), int(tn.nontemporal),
                                  int(tn.chunk_z), int(tn.xcd_remap), stream_handle(T), True,
-                                 *_uniform_args(tn, iCp))
+                                 *_uniform_args(tn, iCp), fast_math=fast)
     elif has_native():
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
-                                 4, 1, 2, 0, 0, 0, 0, False)
+                                 4, 1, 2, 0, 0, 0, 0, False, fast_math=fast)
     else:
         stencil3d_torch(T2, T, iCp, coef, boxes)
 
@@ -199,7 +233,8 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
     T on the six faces. Bitwise equal to K full-interior ``stencil3d_step`` calls
     cropped to the boxes; cells outside the boxes keep T2's values.
     ``tuning.uniform`` as in ``stencil3d_step``: the GPU kernel does not read
-    ``iCp`` then; accepted and ignored on CPU tensors."""
+    ``iCp`` then; accepted and ignored on CPU tensors. ``tuning.fast_math``: every
+    level in the fast7 arithmetic (K = 1 included), on GPU and CPU tensors alike."""
     K = int(K)
     if K not in TEMPORAL_3D:
         raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
@@ -221,16 +256,19 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
     if not boxes:
         return
     coef = StencilCoef3(*coef)
+    fast = _fast_math(tuning, coef)
     if T.is_cuda:
         tn = tuning or Stencil3DTuning()
         native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
                                   tuple(coef), int(tn.rows), int(tn.unroll), int(tn.vec),
                                   int(tn.nontemporal), int(tn.chunk_z), int(tn.xcd_remap),
                                   int(tn.tb_rows), int(tn.tb_chunk_z), int(tn.tb_nontemporal),
-                                  stream_handle(T), True, *_uniform_args(tn, iCp))
+                                  stream_handle(T), True, *_uniform_args(tn, iCp),
+                                  fast_math=fast)
     elif has_native():
         native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
-                                  tuple(coef), 4, 1, 2, 0, 0, 0, 0, 0, 0, 0, False)
+                                  tuple(coef), 4, 1, 2, 0, 0, 0, 0, 0, 0, 0, False,
+                                  fast_math=fast)
     else:
         stencil3dk_torch(K, T2, T, iCp, coef, boxes)
 
