@@ -26,7 +26,25 @@ same rounds, and reports ``vs_canonical`` = canonical median / fast7 median
 (profiles/diffusion3d_fastmath.md); with ``--uniform`` the same for the
 uniform-1/Cp variants.
 
+``--xface W[,W...]`` instead times a pair of x-face boxes of width W (at x0 = 1
+and at x1 = n-1, the x slabs of a frame) through three dispatches in the same
+interleaved rounds: today's (thin-box path up to width 8, else the strip march),
+the x-face path (``Stencil3DTuning.xface``) and, as a reference point, the same
+number of cells as a pair of z slabs. ``vs_today`` = today's median / the
+variant's median. It combines with ``--uniform`` and ``--fast-math``.
+
+``--hide`` instead times ``Diffusion3D`` steps with one rank: ``perf`` with periods
+(0,0,0) (no exchange: the floor), ``perf`` with periods (1,1,1) (the rank is its own
+neighbour on all six sides) and ``perf_hide`` with periods (1,1,1), with the x-face
+path off and on, every model rebuilt in every round so the rounds interleave.
+``recovered`` = (perf periodic - perf_hide) / (perf periodic - perf open). It
+combines with ``--temporal 2``, ``--uniform`` (1/Cp one value: the model's scan
+finds it; without the flag the scan is disabled) and ``--fast-math``
+(profiles/diffusion3d_hide.md).
+
     python bench/stencil3d_sweep.py --sizes 512,1024,1536 --ap 1024 --out sweep3d.json
+    python bench/stencil3d_sweep.py --sizes 256,512,1024 --xface 2,8,16 --out sweep3d_xface.json
+    python bench/stencil3d_sweep.py --sizes 256,512,1024 --hide --out sweep3d_hide.json
     python bench/stencil3d_sweep.py --temporal 2 --out sweep3d_tb.json
     python bench/stencil3d_sweep.py --uniform --out sweep3d_uni.json
     python bench/stencil3d_sweep.py --fast-math --uniform --temporal 2 --out sweep3d_f7.json
@@ -179,6 +197,108 @@ def sweep_size(n: int, a) -> dict:
     return res
 
 
+def _summary(times: dict) -> dict:
+    out = {}
+    for k, t in times.items():
+        med = statistics.median(t)
+        out[k] = {"median_ms": med, "min_ms": min(t), "max_ms": max(t),
+                  "spread": (max(t) - min(t)) / med}
+    return out
+
+
+def sweep_xface(n: int, a) -> dict:
+    """A pair of x-face boxes of every width through today's dispatch, the x-face
+    path and as z slabs of the same cell count."""
+    dev = torch.device("cuda")
+    bufs = [torch.empty((n, n, n), dtype=torch.float64, device=dev) for _ in range(2)]
+    iCp = torch.empty((n, n, n), dtype=torch.float64, device=dev)
+    geom = ops.TileGeometry3(0, 0, 0, n, n, n, 10.0 / n, 10.0 / n, 10.0 / n)
+    ops.init_random3d_(bufs[0], geom, seed=1)
+    bufs[1].copy_(bufs[0])
+    ops.init_random3d_(iCp, geom, seed=2, lo=0.5, hi=2.0)
+    d = 10.0 / n
+    coef = ops.StencilCoef3.from_physics(1.0, d, d, d, d * d / 6.1)
+    flip = [0]
+    variants, cells = {}, {}
+    kinds = [("", ops.Stencil3DTuning())]
+    if a.uniform:
+        kinds.append(("_uni", ops.Stencil3DTuning(uniform=True, uniform_value=1.0)))
+    if a.fast_math:
+        kinds += [(s + "_f7", dataclasses.replace(t, fast_math=True)) for s, t in list(kinds)]
+    for w in a.xface:
+        xb = [(1, 1 + w, 1, n - 1, 1, n - 1), (n - 1 - w, n - 1, 1, n - 1, 1, n - 1)]
+        zb = [(1, n - 1, 1, n - 1, 1, 1 + w), (1, n - 1, 1, n - 1, n - 1 - w, n - 1)]
+        for suffix, tn in kinds:
+            for name, boxes, t in (("today", xb, tn), ("xface", xb, dataclasses.replace(tn, xface=w)),
+                                   ("zslab", zb, tn)):
+                def run(boxes=boxes, t=t):
+                    flip[0] ^= 1
+                    ops.stencil3d_step(bufs[flip[0]], bufs[flip[0] ^ 1], iCp, coef, boxes, t)
+
+                key = f"{name}_w{w}{suffix}"
+                variants[key] = run
+                cells[key] = 2.0 * w * (n - 2) * (n - 2)
+    times = {k: [] for k in variants}
+    for fn in variants.values():
+        fn()
+    torch.cuda.synchronize()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.rounds):
+        for k, fn in variants.items():
+            ev0.record()
+            for _ in range(a.iters):
+                fn()
+            ev1.record()
+            ev1.synchronize()
+            times[k].append(ev0.elapsed_time(ev1) / a.iters)
+    res = _summary(times)
+    for k, r in res.items():
+        per = 16.0 if "_uni" in k else 24.0
+        r["GBps"] = per * cells[k] / r["median_ms"] / 1e6
+        r["vs_today"] = res["today_" + k.split("_", 1)[1]]["median_ms"] / r["median_ms"]
+    del bufs, iCp
+    torch.cuda.empty_cache()
+    return res
+
+
+def sweep_hide(n: int, a) -> dict:
+    """ms per step of perf (open), perf (periodic) and perf_hide (periodic, x-face
+    path off and on) at n^3 with one rank, the models rebuilt in every round."""
+    from rocm_mpi_amd.models import Diffusion3D, Diffusion3DConfig
+
+    cases = {"perf_open": ("perf", (0, 0, 0), 0), "perf_periodic": ("perf", (1, 1, 1), 0),
+             "hide_periodic": ("perf_hide", (1, 1, 1), 0),
+             "hide_periodic_xface": ("perf_hide", (1, 1, 1), None)}
+    steps = a.iters * a.temporal
+    times = {k: [] for k in cases}
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rnd in range(a.rounds + 1):  # round 0 warms every shape and code object
+        for k, (variant, periods, xface) in cases.items():
+            m = Diffusion3D(Diffusion3DConfig(
+                variant=variant, nx=n, ny=n, nz=n, nt=steps, init="random", periods=periods,
+                quiet=True, temporal=a.temporal, fast_math=a.fast_math,
+                uniform_factor=a.uniform, b_width=a.b_width, xface=xface))
+            m.step(2 * a.temporal)
+            m.synchronize()
+            ev0.record()
+            m.step(steps)
+            ev1.record()
+            ev1.synchronize()
+            if rnd:
+                times[k].append(ev0.elapsed_time(ev1) / steps)
+            m.close()
+            del m
+    torch.cuda.empty_cache()
+    res = _summary(times)
+    exposed = res["perf_periodic"]["median_ms"] - res["perf_open"]["median_ms"]
+    for k in ("hide_periodic", "hide_periodic_xface"):
+        gain = res["perf_periodic"]["median_ms"] - res[k]["median_ms"]
+        res[k]["gain_ms"] = gain
+        res[k]["recovered"] = gain / exposed if exposed > 0 else float("nan")
+    res["perf_periodic"]["exposed_ms"] = exposed
+    return res
+
+
 def model_compare(n: int, steps: int) -> dict:
     """Seconds per step of Diffusion3D perf (the kernel) and ap (torch) at n^3."""
     from rocm_mpi_amd.models import Diffusion3D, Diffusion3DConfig
@@ -215,6 +335,12 @@ def main(argv=None) -> int:
     ap.add_argument("--fast-math", dest="fast_math", action="store_true",
                     help="the shipped tuning only, each kernel next to its fast7 twin "
                          "(vs_canonical)")
+    ap.add_argument("--xface", default=[], type=lambda v: [int(x) for x in v.split(",") if x],
+                    help="widths of an x-face box pair: today's dispatch, the x-face path, z slabs")
+    ap.add_argument("--hide", action="store_true",
+                    help="Diffusion3D perf (open, periodic) against perf_hide (periodic)")
+    ap.add_argument("--b-width", dest="b_width", default=(16, 2, 2),
+                    type=lambda v: tuple(int(x) for x in v.split(",")))
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -222,6 +348,16 @@ def main(argv=None) -> int:
     report = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters": a.iters,
               "sizes": {}}
     for n in [int(v) for v in a.sizes.split(",") if v]:
+        if a.xface or a.hide:
+            r = report["sizes"][str(n)] = sweep_xface(n, a) if a.xface else sweep_hide(n, a)
+            for k, v in r.items():
+                print(f"{n:5d}^3 {k:28s} {v['median_ms']:9.4f} ms  spread {v['spread']:.3f}"
+                      + (f"  {v['GBps']:8.1f} GB/s  {v['vs_today']:.3f} x today"
+                         if "vs_today" in v else "")
+                      + (f"  exposed exchange {v['exposed_ms']:.4f} ms" if "exposed_ms" in v else "")
+                      + (f"  gain {v['gain_ms']:.4f} ms, recovered {v['recovered']:.2f}"
+                         if "recovered" in v else ""), flush=True)
+            continue
         report["sizes"][str(n)] = sweep_size(n, a)
         best = sorted((r["median_ms"], k) for k, r in report["sizes"][str(n)].items())
         for ms, k in best:

@@ -213,11 +213,12 @@ PYBIND11_MODULE(_C, m) {
       [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, uintptr_t stream, bool gpu, bool uniform,
-         double uniform_value, bool fast_math) {
+         double uniform_value, bool fast_math, int xface) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
           tn.fast_math = fast_math ? 1 : 0;
+          tn.xface = xface;
           tn.uniform = uniform;
           tn.uniform_value = uniform_value;
           tn.rows = rows;
@@ -242,7 +243,8 @@ PYBIND11_MODULE(_C, m) {
       py::arg("boxes"), py::arg("coef"), py::arg("rows") = 4, py::arg("unroll") = 2,
       py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
       py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true,
-      py::arg("uniform") = false, py::arg("uniform_value") = 0.0, py::arg("fast_math") = false);
+      py::arg("uniform") = false, py::arg("uniform_value") = 0.0, py::arg("fast_math") = false,
+      py::arg("xface") = 0);
   m.def(
       "fast7_ok", [](const Coef5& coef) { return fast7_ok(to_coef3(coef)); }, py::arg("coef"));
   // cells per lane a GPU launch with these arrays runs (stencil3d_vec)

@@ -175,7 +175,8 @@ int64_t count_differing_cpu(const double* A, int64_t n);
 // Fused 7-point stencil on (nz, ny, nx) fields (stencil3d.hip): one explicit
 // 3D diffusion step, T2[b] = f(T, iCp)[b] for every cell of up to kMaxBoxes
 // half-open boxes inside the interior, in ONE launch (StencilCoef3 in
-// rma/common.h has the expression). Throws before any work unless nx, ny,
+// rma/common.h has the expression; with Stencil3DTuning::xface one more launch on
+// the same stream per lanes-per-row class of the face boxes). Throws before any work unless nx, ny,
 // nz >= 3, T2 != T and every non-empty box lies in [1, n-1) per dimension.
 // ---------------------------------------------------------------------------
 constexpr int kMaxBoxes = 8;
@@ -205,7 +206,14 @@ struct Stencil3DTuning {
   // in both kernels, field and uniform paths. Not bitwise equal to canonical;
   // needs fast7_ok(coef) (an invalid argument otherwise, before any work).
   int fast_math = 0;
+  // One-step kernel only: the widest box in x (0..kXfaceMax) that runs the x-face
+  // path (stencil3d.hip: a wave of 64/LX rows of LX = 8, 16 or 32 lanes marching
+  // along z) instead of the thin-box path or the strip march; bitwise the same
+  // result. 0: today's dispatch. Outside 0..kXfaceMax: an invalid argument before
+  // any work. The K-step kernel ignores it: its boxes keep the strip march.
+  int xface = 0;
 };
+constexpr int kXfaceMax = 32;
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
 // Cells per lane both 3D launchers run: tune.vec with even nx and 16-byte

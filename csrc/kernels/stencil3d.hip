@@ -28,6 +28,9 @@
 //     end of a band likewise (wave-uniform). All offsets are 64-bit.
 //   * Odd nx or a base off 16-byte alignment runs the same march with V = 1.
 //     Boxes at most 8 cells wide (frame faces) run one thread per row.
+//   * Stencil3DTuning::xface = W > 0 (opt-in): boxes at most W <= 32 cells wide
+//     run the x-face kernel below instead (rows of 8, 16 or 32 lanes), launched on
+//     the same stream ahead of the march of the remaining boxes.
 //   * Uniform 1/Cp (Stencil3DTuning::uniform, template flag Uni): the factor is a
 //     kernel argument, the array is never dereferenced and no ic registers are
 //     held: 16 B/cell. The same expression in the same order, so bitwise the
@@ -268,6 +271,167 @@ int64_t plan_boxes(BoxList& L, const Box* boxes, int nboxes, int V, int R, int c
   return total;
 }
 
+// ---------------------------------------------------------------------------
+// x-face path (Stencil3DTuning::xface): boxes at most 32 cells wide in x, the
+// x slabs of a frame / interior split. The strip march would load 128 cells a
+// row for them and the thin-box path reads stride-nx scalars; here a wave is
+// 64/LX rows of LX lanes (LX = 8, 16, 32: the smallest >= the box width), lane
+// (r, i) owns cell (ya + r, x0 + i) and marches along z with planes z-1, z, z+1
+// of its cell in registers: every wave-level plane load is 64/LX contiguous row
+// segments of LX*8 bytes, each centre value comes from memory once per task
+// plus two planes per z chunk. x neighbours come from the adjacent lane; lanes
+// i = 0 / LX-1 take theirs from one edge load (lanes of the low half the column
+// left of the box, of the high half column x0+LX). y neighbours come from the
+// lane LX away; rows r = 0 / 64/LX-1 take theirs from one halo-row load.
+// Columns and rows past the box load clamped into the array, which is what the
+// last cell of the box needs from its neighbour lane, and store masked. The
+// loads of plane z+2 and of the edge, halo and 1/Cp values of plane z+1 are
+// issued before the arithmetic of plane z. No LDS, no barrier; 64-bit offsets.
+// The same update3 expression: bitwise the other paths' result.
+// VGPRs / waves per SIMD (build's resource output; no AGPRs, no scratch, no LDS;
+// the same for LX = 8, 16, 32 and both store settings): canonical field 42 / 8,
+// canonical Uni 36 / 8, fast7 field 44 / 8, fast7 Uni 38 / 8. The 120 march
+// instantiations above compile to the registers, scratch and occupancy they had
+// before this path was added (the launcher splits the box list on the host; the
+// march kernel is untouched).
+// ---------------------------------------------------------------------------
+struct FaceList {
+  Box b[kMaxBoxes];
+  int64_t bands[kMaxBoxes];      // wave tasks along y: ceil(rows / (64 / LX))
+  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / waves per block)
+  int64_t chunk_z[kMaxBoxes];    // planes per task
+  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
+  int n;
+};
+
+template <int LX, bool NTS, bool Uni, int A>
+__global__ __launch_bounds__(kBlock) void stencil3d_xface_kernel(double* __restrict__ T2,
+                                                                 const double* __restrict__ T,
+                                                                 Factor<Uni> iCp, int64_t nx,
+                                                                 int64_t ny, FaceList L,
+                                                                 Coef3<A> k) {
+  constexpr int RG = kWave / LX;  // rows of a wave
+  static_assert(LX == 8 || LX == 16 || LX == 32, "lanes per row");
+  const int64_t b = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int bi = 0;
+  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
+  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const Box box = L.b[bi];
+  // block lb of a box: the group of 4 bands fastest, then the z chunk
+  const int64_t band = (lb % L.groups[bi]) * kWavesPerBlock + wave;
+  const int64_t zc = lb / L.groups[bi];
+  if (band >= L.bands[bi]) return;  // the whole wave
+  const int64_t plane = nx * ny;
+  const int64_t ya = box.y0 + band * RG;
+  const int64_t za = box.z0 + zc * L.chunk_z[bi];
+  const int64_t zb = min(box.z1, za + L.chunk_z[bi]);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int i = lane % LX, r = lane / LX;
+  const int64_t x = box.x0 + i, y = ya + r;
+  const bool m = x < box.x1 && y < box.y1;
+  const int64_t xc = min(x, nx - 1);
+  const int64_t row = min(y, ny - 1) * nx;
+  const int64_t o = row + xc;
+  const int64_t oe = row + (i < LX / 2 ? box.x0 - 1 : min(box.x0 + LX, nx - 1));
+  const int64_t oh = (r < RG / 2 ? ya - 1 : min(ya + RG, ny - 1)) * nx + xc;
+
+  const double* p = T + za * plane;
+  double bk = p[o - plane], c = p[o], fr = p[o + plane];
+  double e = p[oe], h = p[oh], f;
+  if constexpr (Uni) f = iCp; else f = iCp[za * plane + o];
+  for (int64_t z = za; z < zb; ++z) {
+    // plane z+2 (the last step loads plane zb again, unused) and the edge, halo
+    // and 1/Cp values of plane z+1 <= zb <= nz-1
+    const double* pn = T + (z + 1) * plane;
+    const double fr2 = T[min(z + 2, zb) * plane + o];
+    const double e2 = pn[oe], h2 = pn[oh];
+    double f2;
+    if constexpr (Uni) f2 = iCp; else f2 = iCp[(z + 1) * plane + o];
+    double left = __shfl_up(c, 1), right = __shfl_down(c, 1);
+    double up = __shfl_up(c, LX), dn = __shfl_down(c, LX);
+    if (i == 0) left = e;
+    if (i == LX - 1) right = e;
+    if (r == 0) up = h;
+    if (r == RG - 1) dn = h;
+    const double v = update3<A, Uni>(left, c, right, up, dn, bk, fr, f, k);
+    if (m) {
+      if constexpr (NTS) {
+        __builtin_nontemporal_store(v, T2 + z * plane + o);
+      } else {
+        T2[z * plane + o] = v;
+      }
+    }
+    bk = c;
+    c = fr;
+    fr = fr2;
+    e = e2;
+    h = h2;
+    f = f2;
+  }
+}
+
+// smallest lanes-per-row class of a face box: 0, 1, 2 for LX = 8, 16, 32
+int face_class(const Box& b) {
+  const int64_t w = b.x1 - b.x0;
+  return w <= 8 ? 0 : w <= 16 ? 1 : 2;
+}
+
+int64_t plan_faces(FaceList& L, const Box* boxes, int nboxes, int LX, int chunk_z) {
+  L = FaceList{};
+  int64_t total = 0;
+  const int64_t rg = kWave / LX;
+  for (int i = 0; i < nboxes; ++i) {
+    const Box& b = boxes[i];
+    const int n = L.n++;
+    L.b[n] = b;
+    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
+    L.bands[n] = (nyb + rg - 1) / rg;
+    L.groups[n] = (L.bands[n] + kWavesPerBlock - 1) / kWavesPerBlock;
+    // 16 planes per task by default: a face has few cells, shorter tasks keep
+    // more waves in flight for the 2/16 re-read of the planes around a chunk
+    L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : 16, nzb);
+    total += L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
+    L.block_end[n] = total;
+  }
+  return total;
+}
+
+template <int LX, int A>
+void launch_face(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
+                 int64_t nx, int64_t ny, const FaceList& L, const Coef3<A>& c, bool uni,
+                 double fac) {
+  const dim3 block(kBlock);
+  if (uni) {
+    if (nt & 1)
+      stencil3d_xface_kernel<LX, true, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny, L, c);
+    else
+      stencil3d_xface_kernel<LX, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny, L, c);
+  } else if (nt & 1) {
+    stencil3d_xface_kernel<LX, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L, c);
+  } else {
+    stencil3d_xface_kernel<LX, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L, c);
+  }
+}
+
+// the face boxes of one launch, one kernel launch per lanes-per-row class in use
+template <int A>
+void launch_faces(const Box (&face)[3][kMaxBoxes], const int (&nface)[3], int chunk_z,
+                  hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
+                  int64_t nx, int64_t ny, const Coef3<A>& c, bool uni, double fac) {
+  for (int cls = 0; cls < 3; ++cls) {
+    if (!nface[cls]) continue;
+    FaceList L{};
+    const int64_t total = plan_faces(L, face[cls], nface[cls], 8 << cls, chunk_z);
+    RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
+    const dim3 grid((unsigned)total);
+    if (cls == 0) launch_face<8, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, uni, fac);
+    else if (cls == 1) launch_face<16, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, uni, fac);
+    else launch_face<32, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, uni, fac);
+    RMA_HIP_LAUNCH_CHECK();
+  }
+}
+
 template <int V, int R, int U, int A>
 void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
                int64_t nx, int64_t ny, const BoxList& L, const Coef3<A>& c, int remap,
@@ -339,29 +503,60 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   RMA_CHECK_ARG(tune.chunk_z >= 0, "chunk_z=" << tune.chunk_z);
   RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
                 "fast_math: fast7 needs lam != 0 and finite coefficients");
+  RMA_CHECK_ARG(tune.xface >= 0 && tune.xface <= kXfaceMax,
+                "xface=" << tune.xface << " (0: off, or the widest face box, up to "
+                         << kXfaceMax << ")");
+  hipStream_t s = as_stream(stream);
+  // xface > 0: boxes at most that wide leave the list for the x-face kernel, the
+  // rest run the march as before. xface = 0: the caller's list, today's dispatch.
+  Box wide[kMaxBoxes], face[3][kMaxBoxes];
+  int nwide = 0, nface[3] = {0, 0, 0};
+  if (tune.xface > 0) {
+    for (int i = 0; i < nboxes; ++i) {
+      const Box& b = boxes[i];
+      if (b.empty()) continue;
+      if (b.x1 - b.x0 <= tune.xface) {
+        const int cls = face_class(b);
+        face[cls][nface[cls]++] = b;
+      } else {
+        wide[nwide++] = b;
+      }
+    }
+    boxes = wide;
+    nboxes = nwide;
+  }
+  const bool faces = nface[0] + nface[1] + nface[2] > 0;
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
   const int64_t total = plan_boxes(L, boxes, nboxes, V, tune.rows, tune.chunk_z);
-  if (L.n == 0) return;
+  if (L.n == 0 && !faces) return;
   RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
   const dim3 grid((unsigned)total);
-  hipStream_t s = as_stream(stream);
   const int remap = tune.xcd_remap ? 1 : 0;
   if (tune.fast_math) {  // the uniform variant takes g = gs * value, formed here
     const Fast7 f = fast7_constants(c);
     const double g = f.gs * tune.uniform_value;
+    if (faces)
+      launch_faces<kFast7>(face, nface, tune.chunk_z, s, tune.nontemporal, T2, T, iCp, nx, ny, f,
+                           tune.uniform, g);
+    if (L.n == 0) return;
     if (V == 2)
       launch_ru<2, kFast7>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny,
                            L, f, remap, tune.uniform, g);
     else
       launch_ru<1, kFast7>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny,
                            L, f, remap, tune.uniform, g);
-  } else if (V == 2) {
-    launch_ru<2, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
-                              ny, L, c, remap, tune.uniform, tune.uniform_value);
   } else {
-    launch_ru<1, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
-                              ny, L, c, remap, tune.uniform, tune.uniform_value);
+    if (faces)
+      launch_faces<kCanonical3>(face, nface, tune.chunk_z, s, tune.nontemporal, T2, T, iCp, nx,
+                                ny, c, tune.uniform, tune.uniform_value);
+    if (L.n == 0) return;
+    if (V == 2)
+      launch_ru<2, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
+                                ny, L, c, remap, tune.uniform, tune.uniform_value);
+    else
+      launch_ru<1, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
+                                ny, L, c, remap, tune.uniform, tune.uniform_value);
   }
   RMA_HIP_LAUNCH_CHECK();
 }

@@ -32,7 +32,9 @@
 //     and are the default. Blocks are ordered per XCD (xcd_remap) as in the
 //     one-step kernel: four waves of a block own four adjacent bands of one strip.
 //   * Odd nx or a base off 16-byte alignment runs the same march with V = 1.
-//     Every box runs the strip march (no thin-box path).
+//     Every box runs the strip march (no thin-box path, and no x-face path:
+//     Stencil3DTuning::xface acts on the one-step kernel only, so the x slabs of
+//     a two-step frame keep the strip march).
 //
 // VGPRs / waves per SIMD at K = 2 (build's resource output; no AGPRs, no scratch):
 // (V, R) = (2, 2) 162 / 3, (2, 4) 230 / 2, (1, 2) 98 / 4, (1, 4) 132 / 3, the same

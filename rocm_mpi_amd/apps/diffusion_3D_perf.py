@@ -29,7 +29,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dims", type=_triple, default=(0, 0, 0), help="process grid a,b,c")
     ap.add_argument("--periods", type=_triple, default=(0, 0, 0))
     ap.add_argument("--init", choices=["gaussian", "random"], default="gaussian")
-    ap.add_argument("--variant", choices=["perf", "ap"], default="perf")
+    ap.add_argument("--variant", choices=["perf", "ap", "perf_hide"], default="perf",
+                    help="perf_hide: boundary frame and halo exchange on a high-priority stream "
+                         "next to the interior update (bitwise the perf field)")
+    ap.add_argument("--b-width", dest="b_width", type=_triple, default=(16, 2, 2),
+                    help="perf_hide boundary width a,b,c in cells from the array edge")
+    ap.add_argument("--xface", type=int, default=0,
+                    help="perf_hide: widest frame box on the one-step kernel's x-face path "
+                         "(0: off, -1: the x boundary width)")
     ap.add_argument("--device", default=None, help="cpu, cuda, cuda:N (default: one GPU per rank)")
     ap.add_argument("--transport", default=os.environ.get("RMA_TRANSPORT", "auto"),
                     choices=["auto", "rccl", "ipc", "staged", "gloo", "self"])
@@ -63,6 +70,29 @@ def factor_line(model) -> str:
         why = "1/Cp varies, or RMA_DIAG=uniform_factor=off"
     return (f"[factor] 1/Cp field path, 24 B per cell and pass (read T, read 1/Cp, write T2): "
             f"{why}")
+
+
+def hide_line(model) -> str:
+    """The frame / interior split of the perf_hide passes (rank 0's boxes)."""
+    cfg = model.cfg
+    parts = []
+    for k in sorted({1, cfg.temporal}, reverse=True):
+        frame, inner = model.hide_boxes(k)
+        own = model.owned_box(k)
+        vol = lambda b: (b[1] - b[0]) * (b[3] - b[2]) * (b[5] - b[4])  # noqa: E731
+        share = sum(vol(b) for b in frame) / max(1, vol(own))
+        xf = model.frame_xface() if k == 1 else 0
+        faced = [b for b in frame if b[1] - b[0] <= xf]
+        path = (f"x-face path for {len(faced)} of {len(frame)} frame boxes (width <= {xf})"
+                if faced else "no box on the x-face path"
+                + (" (the two-step kernel has none)" if k > 1 else " (--xface 0)" if not xf else ""))
+        overlap = ("frame + exchange overlap the interior" if frame and inner is not None
+                   and model.device.type == "cuda" else
+                   "boxes in sequence: frame, exchange, interior" if frame and inner is not None
+                   else "no overlap: one launch, then the exchange")
+        parts.append(f"{k}-step passes: frame {frame}, inner {inner}, {100.0 * share:.1f} % of "
+                     f"the cells in the frame, {path}, {overlap}")
+    return f"[hide] b_width {tuple(cfg.b_width)}; " + "; ".join(parts)
 
 
 def grid_line(model) -> str | None:
@@ -117,10 +147,13 @@ def main(argv=None) -> int:
     cfg = Diffusion3DConfig(variant=a.variant, nx=a.nx, ny=a.ny, nz=a.nz, nt=a.nt, init=a.init,
                             dims=a.dims, periods=a.periods, transport=a.transport,
                             device=a.device, check_every=a.check_every, temporal=a.temporal,
-                            uniform_factor=a.uniform_factor, fast_math=a.fast_math)
+                            uniform_factor=a.uniform_factor, fast_math=a.fast_math,
+                            b_width=a.b_width, xface=None if a.xface < 0 else a.xface)
     model = Diffusion3D(cfg)
     if model.g.me == 0:
         print(factor_line(model), flush=True)
+        if a.variant == "perf_hide":
+            print(hide_line(model), flush=True)
     gline = grid_line(model) if a.temporal > 1 else None
     if gline and model.g.me == 0:
         print(gline, flush=True)

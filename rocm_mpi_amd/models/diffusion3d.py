@@ -10,8 +10,13 @@ Gaussian on cell centres or the counter-based random field.
           CPU twin), swap, then ``update_halo_(T)`` -- serial, as the
           reference's ``diffusion_2D_perf.jl:47-52``.
 ``ap``    the same update as torch tensor expressions.
+``perf_hide``  the perf pass split into a boundary frame and an interior box
+          (``ops.hide_boxes3d``, ImplicitGlobalGrid's ``@hide_communication``
+          with boundary width ``b_width``): the frame runs on a high-priority
+          stream with ``update_halo_`` right behind it, the interior on a
+          low-priority stream next to both. Bitwise the ``perf`` field.
 
-Both compute the canonical per-cell expression (``ops.StencilCoef3``), so their
+All compute the canonical per-cell expression (``ops.StencilCoef3``), so their
 fields agree bitwise, with each other and across decompositions.
 
 ``temporal=2`` (perf only) runs two steps per kernel pass (temporal blocking,
@@ -39,10 +44,44 @@ the plan, of the decomposition, of the uniform-factor path and of the device
 canonical field, not bitwise equal to it. It combines with ``temporal`` and with
 the uniform-factor scan unchanged.
 
-Out of scope here (the 2D model has them): overlap of the boundary update with
-the interior, passes deeper than two steps, a pass planner and the native
-executor (every pass is issued from Python), checkpointing and direct-store
-halos.
+``perf_hide`` in detail. ``b_width[d]`` (default ``(16, 2, 2)``, the reference's
+3D example) counts cells from the array edge; on a side with a neighbour the
+interior box starts ``max(b_width[d], overlap[d])`` cells in, a side without a
+neighbour has no frame slab. Per pass of ``plan(n)`` on a GPU, enqueued in this
+order so that a transport whose exchange blocks the host still overlaps:
+
+1. the frame boxes, one ``ops`` launch on the high-priority stream H;
+2. the interior box on the low-priority stream L;
+3. ``update_halo_(T2)`` on H; then the buffers swap.
+
+Streams and events are created once per model; ordering is by events only, no
+host synchronisation. At the start of ``step`` H and L wait for the caller's
+current stream, at its end the current stream waits for both, so ``step`` stays
+asynchronous and ``field``, ``check_finite`` and ``gather_interior`` stay correct
+on the current stream. Between passes the light protocol ships (not the full
+join): with X the buffer pass p writes and Y the one it reads,
+
+* H's frame of pass p+1 waits for L's interior of pass p: it reads interior
+  cells of X and overwrites frame cells of Y, which that interior read. The
+  exchange of pass p precedes it on H in stream order.
+* L's interior of pass p+1 waits for H's frame kernel of pass p, not for the
+  exchange of pass p: it reads X at least ``overlap - K >= halo width`` cells
+  from the array edge, so never a halo cell, the only cells the exchange
+  writes, and it writes interior cells of Y, which the exchange (it reads send
+  planes of X, all in the frame, and writes halo cells of X) does not touch.
+
+With no neighbour at all, or an interior box empty in some dimension, a pass is
+one launch on the current stream followed by the exchange, as ``perf``. CPU
+tensors run the same boxes in sequence: frame, exchange, interior.
+``temporal``, ``fast_math`` and the uniform-factor scan apply as for ``perf``.
+``xface`` (default 0, decided by profiles/diffusion3d_hide.md): the width up to
+which the frame's boxes run the one-step kernel's x-face path
+(``Stencil3DTuning.xface``); ``None`` takes ``min(max(b_width[0], overlap), 32)``.
+Two-step passes never use it: the two-step kernel has no such path.
+
+Out of scope here (the 2D model has them): passes deeper than two steps, a pass
+planner and the native executor (every pass is issued from Python), frame-first
+fused single-launch passes, checkpointing and direct-store halos.
 """
 from __future__ import annotations
 
@@ -57,7 +96,8 @@ from ..parallel import implicit_grid as gg
 from ..parallel.halo import gather_, update_halo_
 from ..utils import metrics
 
-VARIANTS3D = ("perf", "ap")
+VARIANTS3D = ("perf", "ap", "perf_hide")
+_KERNEL_VARIANTS = ("perf", "perf_hide")  # the fused kernels on double buffers
 # steps per pass whose uniform-factor kernel the model runs when 1/Cp is one value
 # (profiles/diffusion3d_uniform.md); the others keep the field path
 UNIFORM_PASSES_3D = (1, 2)
@@ -94,7 +134,11 @@ class Diffusion3DConfig:
     tuning: ops.Stencil3DTuning | None = None
     temporal: int = 1  # steps per kernel pass (ops.TEMPORAL_3D), perf only
     uniform_factor: bool = True  # uniform-1/Cp kernel variants where 1/Cp is one value
-    fast_math: bool = False  # the fast7 arithmetic in every pass, perf only
+    fast_math: bool = False  # the fast7 arithmetic in every pass, perf / perf_hide only
+    b_width: tuple = (16, 2, 2)  # perf_hide boundary width per dimension, from the array edge
+    # perf_hide: widest frame box on the one-step kernel's x-face path (0: off,
+    # None: min(max(b_width[0], overlap), 32)); profiles/diffusion3d_hide.md
+    xface: int | None = 0
 
     def validate(self) -> None:
         if self.variant not in VARIANTS3D:
@@ -107,10 +151,16 @@ class Diffusion3DConfig:
             raise ValueError("nt >= 1 required")
         if self.temporal not in ops.TEMPORAL_3D:
             raise ValueError(f"temporal must be one of {ops.TEMPORAL_3D}")
-        if self.temporal > 1 and self.variant != "perf":
-            raise ValueError("temporal blocking applies to the perf variant")
-        if self.fast_math and self.variant != "perf":
-            raise ValueError("fast_math applies to the perf variant")
+        if self.temporal > 1 and self.variant not in _KERNEL_VARIANTS:
+            raise ValueError("temporal blocking applies to the perf variant (and perf_hide)")
+        if self.fast_math and self.variant not in _KERNEL_VARIANTS:
+            raise ValueError("fast_math applies to the perf variant (and perf_hide)")
+        if self.variant == "perf_hide":
+            bw = tuple(self.b_width)
+            if len(bw) != 3 or any(int(b) != b or b < 1 for b in bw):
+                raise ValueError(f"b_width must be three integers >= 1, got {self.b_width}")
+            if self.xface is not None and not 0 <= int(self.xface) <= ops.XFACE_MAX:
+                raise ValueError(f"xface must be None or 0..{ops.XFACE_MAX}, got {self.xface}")
 
 
 class Diffusion3D:
@@ -161,7 +211,8 @@ class Diffusion3D:
         self.rescan_factor()
         self.T = torch.empty((nz, ny, nx), **f64)
         self.init_field(self.T)
-        self.T2 = self.T.clone() if cfg.variant == "perf" else None
+        self.T2 = self.T.clone() if cfg.variant in _KERNEL_VARIANTS else None
+        self._hide = None  # perf_hide on a GPU: (H, L, events), created at the first step
         if cfg.variant == "ap":  # flux arrays of the interior rows, preallocated
             self.qx = torch.empty((nz - 2, ny - 2, nx - 1), **f64)
             self.qy = torch.empty((nz - 2, ny - 1, nx - 2), **f64)
@@ -227,7 +278,8 @@ class Diffusion3D:
     def uniform_passes(self) -> tuple:
         """Steps per pass whose kernel runs its uniform-factor variant now: the
         perf passes on a GPU, after a scan that found one value."""
-        if not (self._uniform and self.cfg.variant == "perf" and self.device.type == "cuda"):
+        if not (self._uniform and self.cfg.variant in _KERNEL_VARIANTS
+                and self.device.type == "cuda"):
             return ()
         return tuple(k for k in sorted({1, self.cfg.temporal}) if k in UNIFORM_PASSES_3D)
 
@@ -253,10 +305,13 @@ class Diffusion3D:
         # scan must be seen before they run
         if self.iCp._version != self._iCp_scanned:
             self.rescan_factor()
-        if self.cfg.variant != "perf":
+        if self.cfg.variant == "ap":
             for _ in range(int(n)):
                 self._step_ap()
                 self.steps_done += 1
+            return
+        if self.cfg.variant == "perf_hide":
+            self._step_hide(n)
             return
         for k in self.plan(n):
             if k == 1:
@@ -267,6 +322,92 @@ class Diffusion3D:
             self.T, self.T2 = self.T2, self.T
             update_halo_(self.T)
             self.steps_done += k
+
+    # ------------------------------------------------------------------
+    def hide_boxes(self, k: int) -> tuple:
+        """(frame boxes, interior box | None) of a k-step perf_hide pass."""
+        g = self.g
+        sides = [(g.neighbors[d][0] >= 0, g.neighbors[d][1] >= 0) for d in (0, 1, 2)]
+        return ops.hide_boxes3d((self.cfg.nx, self.cfg.ny, self.cfg.nz), self.owned_box(k),
+                                sides, g.overlaps, self.cfg.b_width)
+
+    def frame_xface(self) -> int:
+        """Stencil3DTuning.xface of the frame launch of a one-step perf_hide pass."""
+        xf = self.cfg.xface
+        if xf is None:
+            xf = min(max(int(self.cfg.b_width[0]), int(self.g.overlaps[0])), ops.XFACE_MAX)
+        return int(xf)
+
+    def _launch(self, k: int, boxes, frame: bool = False) -> None:
+        """One k-step launch T -> T2 on the boxes, on the current stream."""
+        tn = self._tuning(k)
+        if k == 1:
+            if frame and self.frame_xface():
+                tn = dataclasses.replace(tn or ops.Stencil3DTuning(), xface=self.frame_xface())
+            ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, boxes, tuning=tn)
+        else:
+            ops.stencil3dk_step(k, self.T2, self.T, self.iCp, self.coef, boxes, tuning=tn)
+
+    def _step_hide(self, n: int) -> None:
+        """The passes of plan(n), frame / exchange overlapped with the interior
+        (module docstring: streams, events and the read / write sets)."""
+        plan = self.plan(n)
+        split = {k: self.hide_boxes(k) for k in set(plan)}
+        gpu = self.device.type == "cuda"
+        overlapped = gpu and any(fr and inner is not None for fr, inner in split.values())
+        if overlapped:
+            if self._hide is None:
+                # torch: a lower number is a higher priority, 0 the default one
+                self._hide = (torch.cuda.Stream(self.device, priority=-1),
+                              torch.cuda.Stream(self.device, priority=0),
+                              [torch.cuda.Event() for _ in range(4)])
+            H, L, (ev_in, ev_frame, ev_inner, ev_halo) = self._hide
+            cur = torch.cuda.current_stream(self.device)
+            ev_in.record(cur)
+            H.wait_event(ev_in)
+            L.wait_event(ev_in)
+            # the first pass waits on these as on "the pass before"
+            ev_inner.record(L)
+            ev_frame.record(H)
+        for k in plan:
+            frame, inner = split[k]
+            if not frame or inner is None:  # nothing to overlap: the perf pass
+                if overlapped:  # (another k of this plan overlaps) stay ordered on H
+                    H.wait_event(ev_inner)
+                    with torch.cuda.stream(H):
+                        self._launch(k, frame or [inner])
+                        self.T, self.T2 = self.T2, self.T
+                        update_halo_(self.T)
+                    ev_frame.record(H)
+                    L.wait_event(ev_frame)
+                    ev_inner.record(L)
+                else:
+                    self._launch(k, frame or [inner])
+                    self.T, self.T2 = self.T2, self.T
+                    update_halo_(self.T)
+            elif not gpu:  # the same boxes in sequence: frame, exchange, interior
+                self._launch(k, frame, frame=True)
+                update_halo_(self.T2)
+                self._launch(k, [inner])
+                self.T, self.T2 = self.T2, self.T
+            else:
+                H.wait_event(ev_inner)  # interior of the pass before: reads / writes above
+                with torch.cuda.stream(H):
+                    self._launch(k, frame, frame=True)
+                L.wait_event(ev_frame)  # frame kernel of the pass before, not its exchange
+                ev_frame.record(H)
+                with torch.cuda.stream(L):
+                    self._launch(k, [inner])
+                ev_inner.record(L)
+                with torch.cuda.stream(H):
+                    update_halo_(self.T2)
+                self.T, self.T2 = self.T2, self.T
+            self.steps_done += k
+        if overlapped:
+            cur = torch.cuda.current_stream(self.device)
+            ev_halo.record(H)
+            cur.wait_event(ev_halo)
+            cur.wait_event(ev_inner)
 
     def _step_ap(self) -> None:
         """The canonical update as torch expressions (same operation order)."""
@@ -334,6 +475,8 @@ class Diffusion3D:
         res.extra["nz"] = cfg.nz
         res.extra["nzg"] = g.nxyz_g[2]
         res.extra["fast_math"] = bool(cfg.fast_math)
+        if cfg.variant == "perf_hide":
+            res.extra["b_width"] = [int(b) for b in cfg.b_width]
         if g.me == 0 and not cfg.quiet:
             print(metrics.reference_line(nt, wtime, teff), flush=True)
         return res

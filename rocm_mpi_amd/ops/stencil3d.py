@@ -68,7 +68,14 @@ class Stencil3DTuning:
     of about 30) in both kernels, field and uniform paths alike. Rounding-close to
     the canonical update, not bitwise equal to it. CPU tensors honour it: they run
     the fast7 C++ twin, bitwise equal to the GPU kernels. It needs the native
-    extension and a coefficient set that passes ``fast7_ok``."""
+    extension and a coefficient set that passes ``fast7_ok``.
+
+    ``xface`` (one-step kernel only, 0..32, default 0 = today's dispatch): the
+    widest box in x that runs the x-face path of csrc/kernels/stencil3d.hip, a
+    wave of 64/LX rows of LX = 8, 16 or 32 lanes marching along z, instead of the
+    thin-box path (widths up to 8) or the 128-cell strip march. Bitwise the same
+    result. CPU tensors accept and ignore it; the two-step kernel does not have
+    the path."""
 
     rows: int = 4
     unroll: int = 2
@@ -82,8 +89,10 @@ class Stencil3DTuning:
     uniform: bool = False
     uniform_value: float | None = None  # None: read iCp[0, 0, 0] (synchronises the device)
     fast_math: bool = False
+    xface: int = 0
 
 
+XFACE_MAX = 32  # widest box the x-face path takes (Stencil3DTuning.xface)
 # every (rows, unroll) the launcher instantiates
 TUNINGS_3D = ((2, 1), (2, 2), (4, 1), (4, 2), (8, 1))
 # steps per pass stencil3dk_step runs (csrc/kernels/stencil3d_tb.hip stencil3dk_has)
@@ -136,6 +145,53 @@ def validate_boxes(boxes: Sequence[Box], nx: int, ny: int, nz: int) -> list[Box]
                              f"[1,{nx - 1})x[1,{ny - 1})x[1,{nz - 1})")
         out.append((x0, x1, y0, y1, z0, z1))
     return out
+
+
+def hide_boxes3d(n: Sequence[int], owned: Box, sides: Sequence[Sequence[bool]],
+                 overlaps: Sequence[int], b_width: Sequence[int]):
+    """Frame / interior split of the cells a pass writes (``@hide_communication``):
+    ``(frame_boxes, inner_box | None)``.
+
+    ``n = (nx, ny, nz)``; ``owned`` is ``Diffusion3D.owned_box(k)``;
+    ``sides[d] = (has_low_neighbour, has_high_neighbour)`` (a rank that is its own
+    periodic neighbour has one); ``b_width[d] >= 1`` is the boundary width in cells
+    from the array edge. On a side with a neighbour the inner box starts
+    ``max(b_width[d], overlaps[d])`` cells from the array edge, so the send planes
+    ``[ol-hw, ol)`` and ``[n-ol, n-ol+hw)`` lie in the frame; a side without one has
+    no frame slab and the inner box reaches the owned bound. The frame is ``owned``
+    minus the inner box as at most six disjoint slabs: z slabs over the full owned
+    x-y extent, y slabs over the inner z range, x slabs over the inner y and z
+    range; empty slabs are dropped. An inner box empty in some dimension gives
+    ``([owned], None)``, no neighbour at all ``([], owned)``."""
+    n = tuple(int(v) for v in n)
+    bw = tuple(int(v) for v in b_width)
+    ol = tuple(int(v) for v in overlaps)
+    if len(n) != 3 or len(bw) != 3 or len(ol) != 3 or len(sides) != 3 or len(owned) != 6:
+        raise ValueError("hide_boxes3d takes three dimensions: n, sides, overlaps, b_width of "
+                         "length 3 and a box of 6 bounds")
+    if min(bw) < 1:
+        raise ValueError(f"b_width >= 1 required, got {bw}")
+    own = tuple(int(v) for v in owned)
+    if not any(bool(s) for d in range(3) for s in sides[d]):
+        return [], own
+    inner = []
+    for d in range(3):
+        lo, hi = own[2 * d], own[2 * d + 1]
+        m = max(bw[d], ol[d])
+        if sides[d][0]:
+            lo = max(lo, m)
+        if sides[d][1]:
+            hi = min(hi, n[d] - m)
+        if hi <= lo:
+            return [own], None
+        inner += [lo, hi]
+    ox0, ox1, oy0, oy1, oz0, oz1 = own
+    ix0, ix1, iy0, iy1, iz0, iz1 = inner
+    slabs = [(ox0, ox1, oy0, oy1, oz0, iz0), (ox0, ox1, oy0, oy1, iz1, oz1),
+             (ox0, ox1, oy0, iy0, iz0, iz1), (ox0, ox1, iy1, oy1, iz0, iz1),
+             (ox0, ix0, iy0, iy1, iz0, iz1), (ix1, ox1, iy0, iy1, iz0, iz1)]
+    frame = [b for b in slabs if b[1] > b[0] and b[3] > b[2] and b[5] > b[4]]
+    return frame, tuple(inner)
 
 
 def stencil3d_torch(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, c: StencilCoef3,
@@ -195,7 +251,12 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
     T2[b] = T[b] + dt*iCp*(div q)[b]. Cells outside the boxes keep T2's values.
     ``tuning.uniform`` runs the GPU kernel's uniform-factor variant (the array is
     validated but not read); on CPU tensors it is accepted and ignored.
-    ``tuning.fast_math`` runs the fast7 arithmetic, on GPU and CPU tensors alike."""
+    ``tuning.fast_math`` runs the fast7 arithmetic, on GPU and CPU tensors alike.
+    ``tuning.xface`` sends boxes at most that wide in x through the GPU kernel's
+    x-face path (bitwise the same cells); CPU tensors accept and ignore it."""
+    xface = int(tuning.xface) if tuning is not None else 0
+    if not 0 <= xface <= XFACE_MAX:
+        raise ValueError(f"xface={xface} (0: off, or the widest face box, up to {XFACE_MAX})")
     check_field("T", T)
     if T.dim() != 3:
         raise ValueError(f"T must be a (nz, ny, nx) field, got shape {tuple(T.shape)}")
@@ -217,7 +278,7 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  int(tn.rows), int(tn.unroll), int(tn.vec), int(tn.nontemporal),
                                  int(tn.chunk_z), int(tn.xcd_remap), stream_handle(T), True,
-                                 *_uniform_args(tn, iCp), fast_math=fast)
+                                 *_uniform_args(tn, iCp), fast_math=fast, xface=xface)
     elif has_native():
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  4, 1, 2, 0, 0, 0, 0, False, fast_math=fast)
