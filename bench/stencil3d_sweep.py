@@ -42,7 +42,16 @@ combines with ``--temporal 2``, ``--uniform`` (1/Cp one value: the model's scan
 finds it; without the flag the scan is disabled) and ``--fast-math``
 (profiles/diffusion3d_hide.md).
 
+``--native`` instead times ``Diffusion3D`` steps issued pass by pass from Python
+against the native time loop (``Diffusion3DConfig(native=True)``,
+csrc/runtime/executor3d.cpp) of the same build: ``perf`` and ``perf_hide``, one rank
+that is its own periodic neighbour on six sides, uniform 1/Cp, ``--iters`` passes of
+``--temporal`` steps per timing, every model rebuilt in every round. ``median_ms`` is
+GPU time per step, ``enqueue_ms`` host time per step until ``step`` returns;
+``vs_python`` = Python median / native median (profiles/diffusion3d_native.md).
+
     python bench/stencil3d_sweep.py --sizes 512,1024,1536 --ap 1024 --out sweep3d.json
+    python bench/stencil3d_sweep.py --sizes 128,256 --native --iters 200 --rounds 7
     python bench/stencil3d_sweep.py --sizes 256,512,1024 --xface 2,8,16 --out sweep3d_xface.json
     python bench/stencil3d_sweep.py --sizes 256,512,1024 --hide --out sweep3d_hide.json
     python bench/stencil3d_sweep.py --temporal 2 --out sweep3d_tb.json
@@ -299,6 +308,55 @@ def sweep_hide(n: int, a) -> dict:
     return res
 
 
+def sweep_native(n: int, a) -> dict:
+    """ms per step of the Python-issued loop and of the native loop
+    (Diffusion3DConfig.native) at n^3: perf and perf_hide, one rank that is its own
+    periodic neighbour on six sides, uniform 1/Cp, the models rebuilt in every round.
+    ``median_ms``: GPU time per step between two events around step(n) (what a
+    run delivers); ``enqueue_ms``: host time per step until step(n) returns,
+    nothing synchronised (what the loop costs the host)."""
+    import time
+
+    from rocm_mpi_amd.models import Diffusion3D, Diffusion3DConfig
+
+    cases = {f"{v}_{loop}": (v, loop == "native") for v in ("perf", "perf_hide")
+             for loop in ("python", "native")}
+    steps = a.iters * a.temporal
+    times = {k: [] for k in cases}
+    host = {k: [] for k in cases}
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rnd in range(a.rounds + 1):  # round 0 warms every shape and code object
+        for k, (variant, nat) in cases.items():
+            m = Diffusion3D(Diffusion3DConfig(
+                variant=variant, nx=n, ny=n, nz=n, nt=steps, init="random", periods=(1, 1, 1),
+                quiet=True, temporal=a.temporal, fast_math=a.fast_math, uniform_factor=True,
+                b_width=a.b_width, native=nat))
+            assert m.native_loop == nat and m.uniform_factor
+            m.step(2 * a.temporal)
+            m.synchronize()
+            ev0.record()
+            t0 = time.perf_counter()
+            m.step(steps)
+            t1 = time.perf_counter()
+            ev1.record()
+            ev1.synchronize()
+            if rnd:
+                times[k].append(ev0.elapsed_time(ev1) / steps)
+                host[k].append((t1 - t0) * 1e3 / steps)
+            m.close()
+            del m
+    torch.cuda.empty_cache()
+    res = _summary(times)
+    for k, r in res.items():
+        r["enqueue_ms"] = statistics.median(host[k])
+        r["enqueue_spread"] = (max(host[k]) - min(host[k])) / r["enqueue_ms"]
+    for v in ("perf", "perf_hide"):  # > 1: the native loop is ahead
+        py, nat = res[v + "_python"], res[v + "_native"]
+        nat["vs_python"] = py["median_ms"] / nat["median_ms"]
+        nat["enqueue_vs_python"] = py["enqueue_ms"] / nat["enqueue_ms"]
+    return res
+
+
 def model_compare(n: int, steps: int) -> dict:
     """Seconds per step of Diffusion3D perf (the kernel) and ap (torch) at n^3."""
     from rocm_mpi_amd.models import Diffusion3D, Diffusion3DConfig
@@ -339,6 +397,9 @@ def main(argv=None) -> int:
                     help="widths of an x-face box pair: today's dispatch, the x-face path, z slabs")
     ap.add_argument("--hide", action="store_true",
                     help="Diffusion3D perf (open, periodic) against perf_hide (periodic)")
+    ap.add_argument("--native", action="store_true",
+                    help="Diffusion3D's Python-issued loop against the native loop (perf, "
+                         "perf_hide; periodic, uniform 1/Cp): ms per step and host enqueue time")
     ap.add_argument("--b-width", dest="b_width", default=(16, 2, 2),
                     type=lambda v: tuple(int(x) for x in v.split(",")))
     ap.add_argument("--out", default="")
@@ -348,15 +409,21 @@ def main(argv=None) -> int:
     report = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters": a.iters,
               "sizes": {}}
     for n in [int(v) for v in a.sizes.split(",") if v]:
-        if a.xface or a.hide:
-            r = report["sizes"][str(n)] = sweep_xface(n, a) if a.xface else sweep_hide(n, a)
+        if a.xface or a.hide or a.native:
+            r = report["sizes"][str(n)] = (sweep_xface(n, a) if a.xface else
+                                           sweep_native(n, a) if a.native else sweep_hide(n, a))
             for k, v in r.items():
                 print(f"{n:5d}^3 {k:28s} {v['median_ms']:9.4f} ms  spread {v['spread']:.3f}"
                       + (f"  {v['GBps']:8.1f} GB/s  {v['vs_today']:.3f} x today"
                          if "vs_today" in v else "")
                       + (f"  exposed exchange {v['exposed_ms']:.4f} ms" if "exposed_ms" in v else "")
                       + (f"  gain {v['gain_ms']:.4f} ms, recovered {v['recovered']:.2f}"
-                         if "recovered" in v else ""), flush=True)
+                         if "recovered" in v else "")
+                      + (f"  enqueue {v['enqueue_ms']:.4f} ms/step (spread "
+                         f"{v['enqueue_spread']:.3f})" if "enqueue_ms" in v else "")
+                      + (f"  {v['vs_python']:.3f} x python (enqueue "
+                         f"{v['enqueue_vs_python']:.2f} x)" if "vs_python" in v else ""),
+                      flush=True)
             continue
         report["sizes"][str(n)] = sweep_size(n, a)
         best = sorted((r["median_ms"], k) for k, r in report["sizes"][str(n)].items())

@@ -15,6 +15,7 @@
 #include "rma/comm.h"
 #include "rma/common.h"
 #include "rma/executor.h"
+#include "rma/executor3d.h"
 #include "rma/gather.h"
 #include "rma/halo.h"
 #include "rma/ipc.h"
@@ -68,6 +69,7 @@ std::vector<Box> to_boxes(const std::vector<Box6>& v) {
                  std::get<5>(t)});
   return b;
 }
+Box6 from_box(const Box& b) { return {b.x0, b.x1, b.y0, b.y1, b.z0, b.z1}; }
 StencilCoef3 to_coef3(const Coef5& c) {
   return {std::get<0>(c), std::get<1>(c), std::get<2>(c), std::get<3>(c), std::get<4>(c)};
 }
@@ -811,6 +813,81 @@ PYBIND11_MODULE(_C, m) {
             return d;
           },
           py::arg("K"));
+
+  // ---------------- 3D diffusion: pass geometry and the native time loop ----------------
+  // the C++ twins of Diffusion3D.owned_box and ops.hide_boxes3d (rma/plan3d.h)
+  m.def(
+      "owned_box3d",
+      [](const std::array<int64_t, 3>& n, const Neighbors& nbr, int k) {
+        return from_box(owned_box3d(n, nbr, k));
+      },
+      py::arg("n"), py::arg("neighbors"), py::arg("k"));
+  m.def(
+      "hide_boxes3d",
+      [](const std::array<int64_t, 3>& n, const Box6& owned, const Sides3& sides,
+         const std::array<int64_t, 3>& overlaps, const std::array<int64_t, 3>& b_width) {
+        const HideBoxes3 h = hide_boxes3d(n, to_boxes({owned})[0], sides, overlaps, b_width);
+        std::vector<Box6> frame;
+        for (const Box& b : h.frame) frame.push_back(from_box(b));
+        py::object inner = py::none();
+        if (h.has_interior) inner = py::cast(from_box(h.interior));
+        return py::make_tuple(frame, inner);
+      },
+      py::arg("n"), py::arg("owned"), py::arg("sides"), py::arg("overlaps"), py::arg("b_width"));
+  py::class_<Diffusion3DExecutor>(m, "Executor3D")
+      .def(py::init([](uintptr_t T, uintptr_t T2, uintptr_t iCp, int64_t nx, int64_t ny,
+                       int64_t nz, int mode, const Coef5& coef, HaloExchanger* halo,
+                       const std::array<int64_t, 3>& overlaps,
+                       const std::array<int64_t, 3>& halowidths, int steps_per_pass,
+                       bool fast_math, const std::array<int64_t, 3>& b_width, int xface,
+                       bool uniform_factor, int rows, int unroll, int vec, int nontemporal,
+                       int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
+                       int tb_nontemporal) {
+             Exec3DParams p;
+             p.mode = mode;
+             p.coef = to_coef3(coef);
+             p.steps_per_pass = steps_per_pass;
+             p.fast_math = fast_math ? 1 : 0;
+             p.b_width = b_width;
+             p.xface = xface;
+             p.uniform_factor = uniform_factor;
+             p.overlaps = overlaps;
+             p.halowidths = halowidths;
+             p.tune.rows = rows;
+             p.tune.unroll = unroll;
+             p.tune.vec = vec;
+             p.tune.nontemporal = nontemporal;
+             p.tune.chunk_z = chunk_z;
+             p.tune.xcd_remap = xcd_remap;
+             p.tune.tb_rows = tb_rows;
+             p.tune.tb_chunk_z = tb_chunk_z;
+             p.tune.tb_nontemporal = tb_nontemporal;
+             py::gil_scoped_release nogil;  // the 1/Cp scan synchronises the device
+             return new Diffusion3DExecutor(P<double>(T), P<double>(T2), P<const double>(iCp), nx,
+                                            ny, nz, p, halo);
+           }),
+           py::arg("T"), py::arg("T2"), py::arg("iCp"), py::arg("nx"), py::arg("ny"),
+           py::arg("nz"), py::arg("mode"), py::arg("coef"), py::arg("halo").none(true) = nullptr,
+           py::arg("overlaps") = std::array<int64_t, 3>{2, 2, 2},
+           py::arg("halowidths") = std::array<int64_t, 3>{1, 1, 1},
+           py::arg("steps_per_pass") = 1, py::arg("fast_math") = false,
+           py::arg("b_width") = std::array<int64_t, 3>{16, 2, 2}, py::arg("xface") = 0,
+           py::arg("uniform_factor") = true, py::arg("rows") = 4, py::arg("unroll") = 2,
+           py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
+           py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0, py::arg("tb_chunk_z") = 0,
+           py::arg("tb_nontemporal") = 0, py::keep_alive<1, 10>())
+      .def(
+          "run", [](Diffusion3DExecutor& e, int64_t n, uintptr_t s) { e.run(n, S(s)); },
+          py::arg("nsteps"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("parity", &Diffusion3DExecutor::parity)
+      .def_property_readonly("uniform", &Diffusion3DExecutor::uniform)
+      .def_property_readonly("uniform_value", &Diffusion3DExecutor::uniform_value)
+      .def("rescan_factor", &Diffusion3DExecutor::rescan_factor,
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("steps_done", &Diffusion3DExecutor::steps_done)
+      .def_property_readonly("passes_done", &Diffusion3DExecutor::passes_done)
+      .def_property_readonly("frame_xface", &Diffusion3DExecutor::frame_xface)
+      .def("plan", &Diffusion3DExecutor::plan, py::arg("nsteps"));
 
   // ---------------- tracing ----------------
   m.def("trace_enable", &trace_enable);

@@ -140,6 +140,55 @@ int rma_executor_parity(const rma_executor* e);
 int rma_executor_check(const rma_executor* e, int64_t* out_fused);
 int rma_executor_destroy(rma_executor* e);
 
+/* ---- 3D heat diffusion: (nz, ny, nx) fields, x fastest (Julia's A[ix,iy,iz]) ----
+ * coef = {-lam, 1/dx, 1/dy, 1/dz, dt} (StencilCoef3, rma/common.h).
+ * One fused 7-point step on the whole interior [1,n-1)^3 of one tile. */
+int rma_diffusion3d_step(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                         int64_t nz, const double coef[5], void* stream);
+/* K steps (1 or 2) in one pass on nboxes (at most 8) half-open boxes of cells,
+ * boxes[6*i..] = (x0, x1, y0, y1, z0, z1) inside the interior; cells outside the
+ * boxes keep T2's values. fast_math != 0: the fast7 arithmetic (rounding-close
+ * to the canonical update, not bitwise equal to it). */
+int rma_diffusion3d_boxes(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                          int64_t ny, int64_t nz, const int64_t* boxes, int nboxes,
+                          const double coef[5], int fast_math, void* stream);
+/* device-side initial conditions of a local 3D tile of the global grid */
+int rma_init_gaussian3d(rma_grid* g, double* T, int64_t nx, int64_t ny, int64_t nz, double dx,
+                        double dy, double dz, double lx, double ly, double lz, void* stream);
+int rma_init_random3d(rma_grid* g, double* A, int64_t nx, int64_t ny, int64_t nz, double dx,
+                      double dy, double dz, uint64_t seed, void* stream);
+
+/* Native 3D time loop (rma/executor3d.h): mode 0 = perf (one kernel per pass,
+ * then the halo exchange), 1 = perf_hide (boundary frame and exchange on a
+ * high-priority stream next to the interior box; b_width = boundary width per
+ * dimension, from the array edge). T holds the field and T2 a copy of it.
+ * steps_per_pass = 1 or 2: two steps per pass need a grid with overlaps >= 4
+ * and halowidths = 2 along every dimension with a neighbour. fast_math != 0:
+ * every pass runs the fast7 arithmetic. xface: 0..32, the widest frame box on
+ * the one-step kernel's x-face path, -1 = min(max(b_width[0], overlap_x), 32).
+ * iCp is examined when the executor is created (after a device
+ * synchronisation): where every cell holds bit for bit one value the passes
+ * take it as a kernel argument and do not read the array (the same field).
+ * After writing to iCp call rma_executor3d_rescan_factor. Bad arguments are
+ * refused before any launch, named in rma_last_error. The executor pins its
+ * grid like the 2D ones: finalize and destroy may come in any order.
+ * Not here: hipGraph replay, frame-first fused passes, a pass planner,
+ * direct-store halos, more than two steps per pass. */
+typedef struct rma_executor3d rma_executor3d;
+int rma_executor3d_create(rma_grid* g, int mode, double* T, double* T2, const double* iCp,
+                          int64_t nx, int64_t ny, int64_t nz, const double coef[5],
+                          const int64_t b_width[3], int steps_per_pass, int fast_math, int xface,
+                          rma_executor3d** out);
+/* enqueue nsteps after the work on `stream`; `stream` waits for them (asynchronous) */
+int rma_executor3d_run(rma_executor3d* e, int64_t nsteps, void* stream);
+/* 0: the field is in T, 1: in T2 */
+int rma_executor3d_parity(const rma_executor3d* e);
+/* nonzero: the last scan found one value in every cell of iCp */
+int rma_executor3d_uniform(const rma_executor3d* e);
+/* scan iCp again (synchronises the device); out_uniform may be NULL */
+int rma_executor3d_rescan_factor(rma_executor3d* e, int* out_uniform);
+int rma_executor3d_destroy(rma_executor3d* e);
+
 #ifdef __cplusplus
 }
 #endif

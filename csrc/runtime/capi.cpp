@@ -14,6 +14,7 @@
 
 #include "rma/comm.h"
 #include "rma/executor.h"
+#include "rma/executor3d.h"
 #include "rma/gather.h"
 #include "rma/halo.h"
 #include "rma/hip_check.h"
@@ -337,6 +338,140 @@ int rma_executor_check(const rma_executor* e, int64_t* out_fused) {
 }
 
 int rma_executor_destroy(rma_executor* e) {
+  return guard([&] {
+    if (!e) return;
+    rma_grid* g = e->grid;
+    delete e;
+    if (g && --g->live_executors == 0 && g->finalized) destroy_grid(g);
+  });
+}
+
+// ---------------- 3D heat diffusion ----------------
+
+namespace {
+rma::StencilCoef3 coef3(const double c[5]) { return {c[0], c[1], c[2], c[3], c[4]}; }
+
+rma::TileGeom3 geom3(const rma_grid* g, int64_t nx, int64_t ny, int64_t nz, double dx, double dy,
+                     double dz) {
+  rma::TileGeom3 t;
+  t.gx0 = (int64_t)g->coords[0] * (g->nxyz[0] - g->overlaps[0]);
+  t.gy0 = (int64_t)g->coords[1] * (g->nxyz[1] - g->overlaps[1]);
+  t.gz0 = (int64_t)g->coords[2] * (g->nxyz[2] - g->overlaps[2]);
+  t.nxg = g->nxyz_g[0];
+  t.nyg = g->nxyz_g[1];
+  t.nzg = g->nxyz_g[2];
+  t.dx = dx;
+  t.dy = dy;
+  t.dz = dz;
+  t.xoff = 0.5 * (double)(g->nxyz[0] - nx) * dx;
+  t.yoff = 0.5 * (double)(g->nxyz[1] - ny) * dy;
+  t.zoff = 0.5 * (double)(g->nxyz[2] - nz) * dz;
+  t.periodx = g->periods[0];
+  t.periody = g->periods[1];
+  t.periodz = g->periods[2];
+  return t;
+}
+}  // namespace
+
+struct rma_executor3d {
+  std::unique_ptr<rma::Diffusion3DExecutor> ex;
+  rma_grid* grid = nullptr;  // pinned: live_executors counts this executor
+};
+
+int rma_diffusion3d_step(double* T2, const double* T, const double* iCp, int64_t nx, int64_t ny,
+                         int64_t nz, const double coef[5], void* stream) {
+  return guard([&] {
+    RMA_CHECK_ARG(coef != nullptr, "coef is NULL");
+    RMA_CHECK_ARG(iCp != nullptr, "iCp is NULL");
+    const rma::Box b{1, nx - 1, 1, ny - 1, 1, nz - 1};
+    rma::stencil3d_boxes_gpu(T2, T, iCp, nx, ny, nz, &b, 1, coef3(coef), rma::Stencil3DTuning{},
+                             stream);
+  });
+}
+
+int rma_diffusion3d_boxes(int K, double* T2, const double* T, const double* iCp, int64_t nx,
+                          int64_t ny, int64_t nz, const int64_t* boxes, int nboxes,
+                          const double coef[5], int fast_math, void* stream) {
+  return guard([&] {
+    RMA_CHECK_ARG(coef != nullptr, "coef is NULL");
+    RMA_CHECK_ARG(iCp != nullptr, "iCp is NULL");
+    RMA_CHECK_ARG(nboxes >= 0 && nboxes <= rma::kMaxBoxes,
+                  "nboxes " << nboxes << " (at most " << rma::kMaxBoxes << ")");
+    RMA_CHECK_ARG(nboxes == 0 || boxes != nullptr, "boxes is NULL");
+    RMA_CHECK_ARG(K == 1 || K == 2, "K " << K << " (1 or 2 steps per pass)");
+    rma::Box b[rma::kMaxBoxes];
+    for (int i = 0; i < nboxes; ++i)
+      b[i] = {boxes[6 * i], boxes[6 * i + 1], boxes[6 * i + 2],
+              boxes[6 * i + 3], boxes[6 * i + 4], boxes[6 * i + 5]};
+    rma::Stencil3DTuning tn;
+    tn.fast_math = fast_math ? 1 : 0;
+    rma::stencil3dk_boxes_gpu(K, T2, T, iCp, nx, ny, nz, b, nboxes, coef3(coef), tn, stream);
+  });
+}
+
+int rma_init_gaussian3d(rma_grid* g, double* T, int64_t nx, int64_t ny, int64_t nz, double dx,
+                        double dy, double dz, double lx, double ly, double lz, void* stream) {
+  return guard([&] {
+    RMA_CHECK_ARG(g != nullptr && T != nullptr, "grid or T is NULL");
+    rma::init_gaussian3d_gpu(T, nx, ny, nz, geom3(g, nx, ny, nz, dx, dy, dz), lx, ly, lz, stream);
+  });
+}
+
+int rma_init_random3d(rma_grid* g, double* A, int64_t nx, int64_t ny, int64_t nz, double dx,
+                      double dy, double dz, uint64_t seed, void* stream) {
+  return guard([&] {
+    RMA_CHECK_ARG(g != nullptr && A != nullptr, "grid or A is NULL");
+    rma::init_random3d_gpu(A, nx, ny, nz, geom3(g, nx, ny, nz, dx, dy, dz), seed, 0.0, 1.0,
+                           stream);
+  });
+}
+
+int rma_executor3d_create(rma_grid* g, int mode, double* T, double* T2, const double* iCp,
+                          int64_t nx, int64_t ny, int64_t nz, const double coef[5],
+                          const int64_t b_width[3], int steps_per_pass, int fast_math, int xface,
+                          rma_executor3d** out) {
+  return guard([&] {
+    RMA_CHECK_ARG(g != nullptr && out != nullptr && coef != nullptr, "grid, out or coef is NULL");
+    RMA_CHECK_ARG(!g->finalized, "grid already finalized");
+    rma::Exec3DParams p;
+    p.mode = mode;
+    p.coef = coef3(coef);
+    p.steps_per_pass = steps_per_pass;
+    p.fast_math = fast_math ? 1 : 0;
+    p.xface = xface;
+    for (int d = 0; d < 3; ++d) {
+      if (b_width) p.b_width[d] = b_width[d];  // NULL: (16, 2, 2)
+      p.overlaps[d] = g->overlaps[d];
+      p.halowidths[d] = g->hw[d];
+    }
+    auto e = std::make_unique<rma_executor3d>();
+    e->ex = std::make_unique<rma::Diffusion3DExecutor>(T, T2, iCp, nx, ny, nz, p, g->halo.get());
+    e->grid = g;
+    ++g->live_executors;
+    *out = e.release();
+  });
+}
+
+int rma_executor3d_run(rma_executor3d* e, int64_t nsteps, void* stream) {
+  return guard([&] {
+    RMA_CHECK_ARG(e != nullptr, "executor is NULL");
+    e->ex->run(nsteps, stream);
+  });
+}
+
+int rma_executor3d_parity(const rma_executor3d* e) { return e->ex->parity(); }
+
+int rma_executor3d_uniform(const rma_executor3d* e) { return e->ex->uniform() ? 1 : 0; }
+
+int rma_executor3d_rescan_factor(rma_executor3d* e, int* out_uniform) {
+  return guard([&] {
+    RMA_CHECK_ARG(e != nullptr, "executor is NULL");
+    const bool u = e->ex->rescan_factor();
+    if (out_uniform) *out_uniform = u ? 1 : 0;
+  });
+}
+
+int rma_executor3d_destroy(rma_executor3d* e) {
   return guard([&] {
     if (!e) return;
     rma_grid* g = e->grid;

@@ -16,12 +16,26 @@
 # The native time loop is exposed too: `ex = DiffusionExecutor(T, T2, iCp,
 # coef; mode=1, steps_per_pass=8)`, `run!(ex, n)` — K steps per kernel pass
 # need init_global_grid(...; overlaps=(2K,2K,2), halowidths=(K,K,1)).
+#
+# 3D heat diffusion (diffusion3D, ImplicitGlobalGrid's flagship example):
+#
+#     init_global_grid(nx, ny, nz; periodx=1, periody=1, periodz=1)
+#     init_gaussian3d!(T, dx, dy, dz, lx, ly, lz); T2 = copy(T)
+#     ex = Diffusion3DExecutor(T, T2, iCp, (-lam, 1/dx, 1/dy, 1/dz, dt); mode=1,
+#                              b_width=(16, 2, 2))
+#     run!(ex, nt); T = current_field(ex)
+#
+# steps_per_pass=2 needs overlaps=(4,4,4), halowidths=(2,2,2). Single kernel
+# calls: diffusion3d_step!(T2, T, iCp, coef), diffusion3d_boxes!(T2, T, iCp, coef,
+# boxes; steps=K). After writing to iCp call rescan_factor!(ex).
 module ImplicitGlobalGridMI355X
 
 using Libdl
 
 export init_global_grid, finalize_global_grid, update_halo!, gather!, gather_rankmajor!, nx_g, ny_g, nz_g,
-       x_g, y_g, z_g, tic, toc, DiffusionExecutor, run!, current_field, check_executor
+       x_g, y_g, z_g, tic, toc, DiffusionExecutor, run!, current_field, check_executor,
+       Diffusion3DExecutor, diffusion3d_step!, diffusion3d_boxes!, init_gaussian3d!,
+       init_random3d!, uniform_factor, rescan_factor!
 
 const LIB = Ref{Ptr{Cvoid}}(C_NULL)
 const GRID = Ref{Ptr{Cvoid}}(C_NULL)
@@ -200,6 +214,103 @@ function check_executor(ex::DiffusionExecutor)
     nf = Ref{Int64}(0)
     check(ccall(sym(:rma_executor_check), Cint, (Ptr{Cvoid}, Ref{Int64}), ex.ptr, nf))
     return nf[]
+end
+
+# ---------------- 3D heat diffusion ----------------
+# Arrays are A[ix,iy,iz] (the native (nz,ny,nx) layout); coef = (-lam, 1/dx, 1/dy, 1/dz, dt).
+
+"""diffusion3d_step!(T2, T, iCp, coef): one fused 7-point step on the whole interior."""
+function diffusion3d_step!(T2, T, iCp, coef::NTuple{5,Float64}; stream::Ptr{Cvoid}=C_NULL)
+    check(ccall(sym(:rma_diffusion3d_step), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                devptr(T2), devptr(T), devptr(iCp), size(T, 1), size(T, 2), size(T, 3),
+                collect(coef), stream))
+    return nothing
+end
+
+"""diffusion3d_boxes!(T2, T, iCp, coef, boxes; steps=1, fast_math=false): `steps` (1 or 2)
+time steps in one pass on at most 8 boxes. A box is (x0, x1, y0, y1, z0, z1), 1-based and
+inclusive as Julia ranges x0:x1 (converted to the C ABI's 0-based half-open bounds)."""
+function diffusion3d_boxes!(T2, T, iCp, coef::NTuple{5,Float64}, boxes; steps::Integer=1,
+                            fast_math::Bool=false, stream::Ptr{Cvoid}=C_NULL)
+    flat = Int64[]
+    for b in boxes
+        append!(flat, (b[1] - 1, b[2], b[3] - 1, b[4], b[5] - 1, b[6]))
+    end
+    check(ccall(sym(:rma_diffusion3d_boxes), Cint,
+                (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Cint,
+                 Ptr{Float64}, Cint, Ptr{Cvoid}),
+                steps, devptr(T2), devptr(T), devptr(iCp), size(T, 1), size(T, 2), size(T, 3),
+                flat, length(boxes), collect(coef), Cint(fast_math), stream))
+    return nothing
+end
+
+"""init_gaussian3d!(T, dx, dy, dz, lx, ly, lz): the reference's initial Gaussian on cell
+centres, computed on the device for this rank's tile of the global grid."""
+function init_gaussian3d!(T, dx, dy, dz, lx, ly, lz; stream::Ptr{Cvoid}=C_NULL)
+    check(ccall(sym(:rma_init_gaussian3d), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Float64, Float64, Float64, Float64,
+                 Float64, Float64, Ptr{Cvoid}),
+                GRID[], devptr(T), size(T, 1), size(T, 2), size(T, 3), dx, dy, dz, lx, ly, lz,
+                stream))
+    return T
+end
+
+"""init_random3d!(A, dx, dy, dz; seed=0): uniform [0,1) keyed by the global cell index (the
+same field for every decomposition)."""
+function init_random3d!(A, dx, dy, dz; seed::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    check(ccall(sym(:rma_init_random3d), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Float64, Float64, Float64, UInt64,
+                 Ptr{Cvoid}),
+                GRID[], devptr(A), size(A, 1), size(A, 2), size(A, 3), dx, dy, dz, UInt64(seed),
+                stream))
+    return A
+end
+
+# Native 3D time loop (mode 0 perf, 1 perf_hide). As DiffusionExecutor, the struct
+# keeps T, T2 and 1/Cp referenced for as long as the native executor lives.
+mutable struct Diffusion3DExecutor
+    ptr::Ptr{Cvoid}
+    T::Any
+    T2::Any
+    iCp::Any
+end
+
+# steps_per_pass = 1 or 2; b_width = perf_hide's boundary width per dimension from the
+# array edge; xface = 0..32 (the widest frame box on the one-step kernel's x-face path,
+# -1: min(max(b_width[1], overlap_x), 32)). T2 must hold a copy of T.
+function Diffusion3DExecutor(T, T2, iCp, coef::NTuple{5,Float64}; mode::Integer=1,
+                             steps_per_pass::Integer=1, b_width=(16, 2, 2),
+                             fast_math::Bool=false, xface::Integer=0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall(sym(:rma_executor3d_create), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64,
+                 Ptr{Float64}, Ptr{Int64}, Cint, Cint, Cint, Ptr{Ptr{Cvoid}}),
+                GRID[], mode, devptr(T), devptr(T2), devptr(iCp), size(T, 1), size(T, 2),
+                size(T, 3), collect(coef), Int64[b_width...], steps_per_pass, Cint(fast_math),
+                xface, out))
+    ex = Diffusion3DExecutor(out[], T, T2, iCp)
+    # pins the native grid like the 2D executor: any finalization order is safe
+    finalizer(e -> ccall(sym(:rma_executor3d_destroy), Cint, (Ptr{Cvoid},), e.ptr), ex)
+    return ex
+end
+
+run!(ex::Diffusion3DExecutor, n::Integer; stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall(sym(:rma_executor3d_run), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}), ex.ptr, n, stream))
+
+current_field(ex::Diffusion3DExecutor) =
+    ccall(sym(:rma_executor3d_parity), Cint, (Ptr{Cvoid},), ex.ptr) == 0 ? ex.T : ex.T2
+
+"""uniform_factor(ex): the last scan found one value in every cell of 1/Cp (the passes
+then take it as a kernel argument and do not read the array)."""
+uniform_factor(ex::Diffusion3DExecutor) =
+    ccall(sym(:rma_executor3d_uniform), Cint, (Ptr{Cvoid},), ex.ptr) != 0
+
+"""rescan_factor!(ex): examine 1/Cp again after writing to it (synchronises the device)."""
+function rescan_factor!(ex::Diffusion3DExecutor)
+    u = Ref{Cint}(0)
+    check(ccall(sym(:rma_executor3d_rescan_factor), Cint, (Ptr{Cvoid}, Ptr{Cint}), ex.ptr, u))
+    return u[] != 0
 end
 
 end # module

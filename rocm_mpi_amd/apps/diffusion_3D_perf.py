@@ -51,7 +51,22 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fast-math", dest="fast_math", action="store_true",
                     help="every pass in the fast7 arithmetic (7-point sum, one folded per-cell "
                          "factor; rounding-level difference from canonical, perf only)")
+    ap.add_argument("--native", action="store_true",
+                    help="perf / perf_hide on a GPU: issue the time loop from C++ "
+                         "(_C.Executor3D) instead of pass by pass from Python; the same field")
     return ap
+
+
+def loop_line(model) -> str:
+    """Who issues the passes of step(n)."""
+    if model.native_loop:
+        return "[loop] native (the C++ time loop, csrc/runtime/executor3d.cpp)"
+    if not model.cfg.native:
+        return "[loop] python (every pass issued from Python; --native: from C++)"
+    why = ("variant ap has no kernel passes" if model.cfg.variant == "ap" else
+           "CPU tensors" if model.device.type != "cuda" else
+           f"transport {model.g.transport} has no native halo engine")
+    return f"[loop] python (--native does not apply: {why})"
 
 
 def factor_line(model) -> str:
@@ -148,9 +163,11 @@ def main(argv=None) -> int:
                             dims=a.dims, periods=a.periods, transport=a.transport,
                             device=a.device, check_every=a.check_every, temporal=a.temporal,
                             uniform_factor=a.uniform_factor, fast_math=a.fast_math,
-                            b_width=a.b_width, xface=None if a.xface < 0 else a.xface)
+                            b_width=a.b_width, xface=None if a.xface < 0 else a.xface,
+                            native=a.native)
     model = Diffusion3D(cfg)
     if model.g.me == 0:
+        print(loop_line(model), flush=True)
         print(factor_line(model), flush=True)
         if a.variant == "perf_hide":
             print(hide_line(model), flush=True)

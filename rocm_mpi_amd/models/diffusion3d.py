@@ -79,9 +79,18 @@ which the frame's boxes run the one-step kernel's x-face path
 (``Stencil3DTuning.xface``); ``None`` takes ``min(max(b_width[0], overlap), 32)``.
 Two-step passes never use it: the two-step kernel has no such path.
 
+``native`` (off by default; perf and perf_hide on a GPU whose grid has a native
+halo engine: the self, rccl, ipc and loopback transports): ``step(n)`` is one call
+into the C++ time loop (csrc/runtime/executor3d.cpp), which enqueues on the
+current stream exactly what is described above, so the field is bitwise the same;
+``T`` / ``T2`` follow its parity and ``rescan_factor()`` is forwarded to it. CPU
+tensors, ``ap`` and the other transports keep the Python-issued loop
+(``native_loop`` says which one runs). profiles/diffusion3d_native.md has the host
+cost of both loops.
+
 Out of scope here (the 2D model has them): passes deeper than two steps, a pass
-planner and the native executor (every pass is issued from Python), frame-first
-fused single-launch passes, checkpointing and direct-store halos.
+planner, hipGraph replay, frame-first fused single-launch passes, checkpointing
+and direct-store halos.
 """
 from __future__ import annotations
 
@@ -139,6 +148,10 @@ class Diffusion3DConfig:
     # perf_hide: widest frame box on the one-step kernel's x-face path (0: off,
     # None: min(max(b_width[0], overlap), 32)); profiles/diffusion3d_hide.md
     xface: int | None = 0
+    # perf / perf_hide on a GPU with a native halo engine: step(n) is enqueued by the
+    # C++ time loop (_C.Executor3D, csrc/runtime/executor3d.cpp) instead of pass by
+    # pass from Python; bitwise the same field (profiles/diffusion3d_native.md)
+    native: bool = False
 
     def validate(self) -> None:
         if self.variant not in VARIANTS3D:
@@ -220,6 +233,56 @@ class Diffusion3D:
             self.dTdt = torch.empty((nz - 2, ny - 2, nx - 2), **f64)
             self._tmp = torch.empty((nz - 2, ny - 2, nx - 2), **f64)
         self.steps_done = 0
+        self._exec = None  # the native time loop (cfg.native), with the two buffers it holds
+        if self.native_loop:
+            try:
+                self._make_executor()
+            except Exception:
+                self.close()
+                raise
+
+    # ------------------------------------------------------------------
+    @property
+    def native_loop(self) -> bool:
+        """step(n) goes to the C++ time loop: cfg.native, a kernel variant, GPU
+        tensors and a native halo engine (the self, rccl, ipc and loopback
+        transports). Everything else keeps the Python-issued loop."""
+        return bool(self.cfg.native and self.cfg.variant in _KERNEL_VARIANTS
+                    and self.device.type == "cuda" and self.g.halo is not None)
+
+    def _make_executor(self) -> None:
+        from .._native import native
+
+        cfg, g = self.cfg, self.g
+        tn = cfg.tuning or ops.Stencil3DTuning()
+        if tn.uniform or tn.fast_math or tn.xface:
+            raise ValueError("native=True sets uniform, fast_math and xface per launch from the "
+                             "config (uniform_factor, fast_math, xface), not from cfg.tuning")
+        self._bufs = (self.T, self.T2)
+        self._exec = native().Executor3D(
+            self.T.data_ptr(), self.T2.data_ptr(), self.iCp.data_ptr(), cfg.nx, cfg.ny, cfg.nz,
+            1 if cfg.variant == "perf_hide" else 0, tuple(self.coef), g.halo,
+            overlaps=[int(o) for o in g.overlaps], halowidths=[int(h) for h in g.halowidths],
+            steps_per_pass=int(cfg.temporal), fast_math=bool(cfg.fast_math),
+            b_width=[int(b) for b in cfg.b_width],
+            xface=-1 if cfg.xface is None else int(cfg.xface),
+            uniform_factor=bool(cfg.uniform_factor), rows=int(tn.rows), unroll=int(tn.unroll),
+            vec=int(tn.vec), nontemporal=int(tn.nontemporal), chunk_z=int(tn.chunk_z),
+            xcd_remap=int(tn.xcd_remap), tb_rows=int(tn.tb_rows), tb_chunk_z=int(tn.tb_chunk_z),
+            tb_nontemporal=int(tn.tb_nontemporal))
+        self._adopt_verdict()
+
+    def _adopt_verdict(self) -> None:
+        """The executor's scan of 1/Cp is the model's."""
+        self._iCp_scanned = self.iCp._version
+        self._uniform = bool(self._exec.uniform)
+        self._factor = float(self._exec.uniform_value) if self._uniform else 0.0
+
+    def _step_native(self, n: int) -> None:
+        self._exec.run(int(n), torch.cuda.current_stream(self.device).cuda_stream)
+        p = self._exec.parity
+        self.T, self.T2 = self._bufs[p], self._bufs[1 - p]
+        self.steps_done += int(n)
 
     # ------------------------------------------------------------------
     def geometry(self) -> ops.TileGeometry3:
@@ -264,6 +327,10 @@ class Diffusion3D:
         the verdict. step() does this by itself after an in-place torch edit;
         call it after a write torch's version counter does not see."""
         off = _factor_diag_off()
+        if getattr(self, "_exec", None) is not None:  # the native loop scans for both
+            self._exec.rescan_factor()
+            self._adopt_verdict()
+            return self._uniform
         self._iCp_scanned = self.iCp._version
         self._uniform, self._factor = False, 0.0
         if self.cfg.uniform_factor and not off and ops.count_differing(self.iCp) == 0:
@@ -305,6 +372,9 @@ class Diffusion3D:
         # scan must be seen before they run
         if self.iCp._version != self._iCp_scanned:
             self.rescan_factor()
+        if self._exec is not None:
+            self._step_native(n)
+            return
         if self.cfg.variant == "ap":
             for _ in range(int(n)):
                 self._step_ap()
@@ -517,6 +587,7 @@ class Diffusion3D:
 
     def close(self) -> None:
         self.synchronize()
+        self._exec = None  # its streams and events go before the grid's halo engine
         if self._owns_grid:
             gg.finalize_global_grid()
             self._owns_grid = False
