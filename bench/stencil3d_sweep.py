@@ -31,12 +31,17 @@ and at x1 = n-1, the x slabs of a frame) through three dispatches in the same
 interleaved rounds: today's (thin-box path up to width 8, else the strip march),
 the x-face path (``Stencil3DTuning.xface``) and, as a reference point, the same
 number of cells as a pair of z slabs. ``vs_today`` = today's median / the
-variant's median. It combines with ``--uniform`` and ``--fast-math``.
+variant's median. It combines with ``--uniform`` and ``--fast-math``. With
+``--temporal 2`` the pair (at x0 = 2 and x1 = n-2, the x slabs of a two-step frame)
+runs through the two-step kernel's two paths instead: the strip march (today's
+dispatch) and its x-face path at rows per group 2 and 4 and every
+``--face-chunk-z`` planes per task (``xface-rR-czC``); GB/s counts one pass.
 
 ``--hide`` instead times ``Diffusion3D`` steps with one rank: ``perf`` with periods
 (0,0,0) (no exchange: the floor), ``perf`` with periods (1,1,1) (the rank is its own
 neighbour on all six sides) and ``perf_hide`` with periods (1,1,1), with the x-face
-path off and on, every model rebuilt in every round so the rounds interleave.
+path off and on (one- and two-step frames alike), every model rebuilt in every round
+so the rounds interleave.
 ``recovered`` = (perf periodic - perf_hide) / (perf periodic - perf open). It
 combines with ``--temporal 2``, ``--uniform`` (1/Cp one value: the model's scan
 finds it; without the flag the scan is disabled) and ``--fast-math``
@@ -54,6 +59,8 @@ GPU time per step, ``enqueue_ms`` host time per step until ``step`` returns;
     python bench/stencil3d_sweep.py --sizes 128,256 --native --iters 200 --rounds 7
     python bench/stencil3d_sweep.py --sizes 256,512,1024 --xface 2,8,16 --out sweep3d_xface.json
     python bench/stencil3d_sweep.py --sizes 256,512,1024 --hide --out sweep3d_hide.json
+    python bench/stencil3d_sweep.py --sizes 256,512,1024 --xface 2,6,14,30 --temporal 2 --uniform --fast-math
+    python bench/stencil3d_sweep.py --sizes 256,512,1024 --hide --temporal 2 --uniform
     python bench/stencil3d_sweep.py --temporal 2 --out sweep3d_tb.json
     python bench/stencil3d_sweep.py --uniform --out sweep3d_uni.json
     python bench/stencil3d_sweep.py --fast-math --uniform --temporal 2 --out sweep3d_f7.json
@@ -234,19 +241,35 @@ def sweep_xface(n: int, a) -> dict:
         kinds.append(("_uni", ops.Stencil3DTuning(uniform=True, uniform_value=1.0)))
     if a.fast_math:
         kinds += [(s + "_f7", dataclasses.replace(t, fast_math=True)) for s, t in list(kinds)]
+    K = a.temporal
+    today = {}  # variant -> today's dispatch of the same boxes, arithmetic and 1/Cp path
     for w in a.xface:
-        xb = [(1, 1 + w, 1, n - 1, 1, n - 1), (n - 1 - w, n - 1, 1, n - 1, 1, n - 1)]
-        zb = [(1, n - 1, 1, n - 1, 1, 1 + w), (1, n - 1, 1, n - 1, n - 1 - w, n - 1)]
+        # one-step: the slabs start at the first interior cell; a K-step pass owns
+        # [K, n-K) next to a neighbour (width-K halos)
+        xb = [(K, K + w, K, n - K, K, n - K), (n - K - w, n - K, K, n - K, K, n - K)]
+        zb = [(K, n - K, K, n - K, K, K + w), (K, n - K, K, n - K, n - K - w, n - K)]
         for suffix, tn in kinds:
-            for name, boxes, t in (("today", xb, tn), ("xface", xb, dataclasses.replace(tn, xface=w)),
-                                   ("zslab", zb, tn)):
+            cases = [("today", xb, tn)]
+            if K == 1:
+                cases.append(("xface", xb, dataclasses.replace(tn, xface=w)))
+            else:  # the two-step face path at every rows x planes-per-task
+                cases += [(f"xface-r{r}-cz{cz}", xb,
+                           dataclasses.replace(tn, xface=w, tb_rows=r, tb_chunk_z=cz))
+                          for r in ops.TB_ROWS_3D for cz in a.face_chunk_z]
+            cases.append(("zslab", zb, tn))
+            for name, boxes, t in cases:
                 def run(boxes=boxes, t=t):
                     flip[0] ^= 1
-                    ops.stencil3d_step(bufs[flip[0]], bufs[flip[0] ^ 1], iCp, coef, boxes, t)
+                    if K == 1:
+                        ops.stencil3d_step(bufs[flip[0]], bufs[flip[0] ^ 1], iCp, coef, boxes, t)
+                    else:
+                        ops.stencil3dk_step(K, bufs[flip[0]], bufs[flip[0] ^ 1], iCp, coef, boxes,
+                                            t)
 
                 key = f"{name}_w{w}{suffix}"
                 variants[key] = run
-                cells[key] = 2.0 * w * (n - 2) * (n - 2)
+                today[key] = f"today_w{w}{suffix}"
+                cells[key] = 2.0 * w * (n - 2 * K) * (n - 2 * K)
     times = {k: [] for k in variants}
     for fn in variants.values():
         fn()
@@ -264,7 +287,7 @@ def sweep_xface(n: int, a) -> dict:
     for k, r in res.items():
         per = 16.0 if "_uni" in k else 24.0
         r["GBps"] = per * cells[k] / r["median_ms"] / 1e6
-        r["vs_today"] = res["today_" + k.split("_", 1)[1]]["median_ms"] / r["median_ms"]
+        r["vs_today"] = res[today[k]]["median_ms"] / r["median_ms"]
     del bufs, iCp
     torch.cuda.empty_cache()
     return res
@@ -385,6 +408,9 @@ def main(argv=None) -> int:
                     help="2: the 2-step pass against two one-step launches")
     ap.add_argument("--tb-chunk-z", dest="tb_chunk_z", default="0,16,64",
                     type=lambda v: [int(x) for x in v.split(",")])
+    ap.add_argument("--face-chunk-z", dest="face_chunk_z", default="16,32",
+                    type=lambda v: [int(x) for x in v.split(",")],
+                    help="--xface --temporal 2: planes per task of the two-step face path")
     ap.add_argument("--ap", type=int, default=0, help="cube size of the perf-versus-ap timing")
     ap.add_argument("--ap-steps", type=int, default=5)
     ap.add_argument("--one", action="store_true", help="default tuning and probes only")

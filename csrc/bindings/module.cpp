@@ -268,11 +268,12 @@ PYBIND11_MODULE(_C, m) {
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
          int tb_nontemporal, uintptr_t stream, bool gpu, bool uniform, double uniform_value,
-         bool fast_math) {
+         bool fast_math, int xface) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
           tn.fast_math = fast_math ? 1 : 0;
+          tn.xface = xface;
           tn.uniform = uniform;
           tn.uniform_value = uniform_value;
           tn.rows = rows;
@@ -302,7 +303,24 @@ PYBIND11_MODULE(_C, m) {
       py::arg("chunk_z") = 0, py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0,
       py::arg("tb_chunk_z") = 0, py::arg("tb_nontemporal") = 0, py::arg("stream") = 0,
       py::arg("gpu") = true, py::arg("uniform") = false, py::arg("uniform_value") = 0.0,
-      py::arg("fast_math") = false);
+      py::arg("fast_math") = false, py::arg("xface") = 0);
+  // the kernel path of every non-empty box of a K-step launch with this xface
+  // (plan_dispatch3d, the rule both launchers run): [(path, lanes), ...] with path
+  // "march", "thin" or "xface". Host only.
+  m.def(
+      "stencil3d_dispatch",
+      [](int K, const std::vector<Box6>& boxes, int xface) {
+        auto b = to_boxes(boxes);
+        Stencil3DTuning tn;
+        tn.xface = xface;
+        std::vector<Dispatch3D> d(b.size());
+        plan_dispatch3d(K, b.data(), (int)b.size(), tn, d.data());
+        std::vector<std::pair<std::string, int>> out;
+        for (const Dispatch3D& e : d)
+          if (e.path != kPathNone) out.emplace_back(path3d_name(e.path), e.lanes);
+        return out;
+      },
+      py::arg("K"), py::arg("boxes"), py::arg("xface") = 0);
   m.def("stencil3dk_has", &stencil3dk_has, py::arg("K"));
   m.def("stencil3dk_has_rows", &stencil3dk_has_rows, py::arg("rows"));
   // Cells of A[0, n) whose bit pattern differs from A[0]'s. GPU: out2 is device

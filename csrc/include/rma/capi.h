@@ -165,7 +165,8 @@ int rma_init_random3d(rma_grid* g, double* A, int64_t nx, int64_t ny, int64_t nz
  * steps_per_pass = 1 or 2: two steps per pass need a grid with overlaps >= 4
  * and halowidths = 2 along every dimension with a neighbour. fast_math != 0:
  * every pass runs the fast7 arithmetic. xface: 0..32, the widest frame box on
- * the one-step kernel's x-face path, -1 = min(max(b_width[0], overlap_x), 32).
+ * the kernels' x-face paths, -1 = min(max(b_width[0], overlap_x), 32); it
+ * applies to one- and two-step frames (two-step: boxes up to 30 wide).
  * iCp is examined when the executor is created (after a device
  * synchronisation): where every cell holds bit for bit one value the passes
  * take it as a kernel argument and do not read the array (the same field).

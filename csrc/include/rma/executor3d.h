@@ -49,8 +49,10 @@ struct Exec3DParams {
   int steps_per_pass = 1;  // K: 1 or 2
   int fast_math = 0;       // every pass, the one-step remainder included, runs fast7
   std::array<int64_t, 3> b_width{16, 2, 2};  // perf_hide boundary width from the array edge
-  // perf_hide: widest frame box on the one-step kernel's x-face path, 0..kXfaceMax;
-  // -1: min(max(b_width[0], overlap_x), kXfaceMax). Two-step passes never use it.
+  // perf_hide: widest frame box on the kernels' x-face paths, 0..kXfaceMax;
+  // -1: min(max(b_width[0], overlap_x), kXfaceMax). It applies to the frame launch
+  // of one- and two-step passes; in a two-step frame boxes wider than 30 keep the
+  // strip march (plan_dispatch3d).
   int xface = 0;
   bool uniform_factor = true;  // uniform-1/Cp kernel variants where the scan allows
   Stencil3DTuning tune{};      // uniform*, fast_math and xface are set per launch

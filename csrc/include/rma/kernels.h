@@ -206,14 +206,36 @@ struct Stencil3DTuning {
   // in both kernels, field and uniform paths. Not bitwise equal to canonical;
   // needs fast7_ok(coef) (an invalid argument otherwise, before any work).
   int fast_math = 0;
-  // One-step kernel only: the widest box in x (0..kXfaceMax) that runs the x-face
-  // path (stencil3d.hip: a wave of 64/LX rows of LX = 8, 16 or 32 lanes marching
-  // along z) instead of the thin-box path or the strip march; bitwise the same
-  // result. 0: today's dispatch. Outside 0..kXfaceMax: an invalid argument before
-  // any work. The K-step kernel ignores it: its boxes keep the strip march.
+  // The widest box in x (0..kXfaceMax) that runs an x-face path instead of the
+  // thin-box path or the strip march; bitwise the same result. One-step kernel
+  // (stencil3d.hip): a wave of 64/LX rows of LX = 8, 16 or 32 lanes marching along
+  // z. K-step kernel (stencil3d_tb.hip): a wave of 64/LX groups of LX lanes, each
+  // group the K-step march of one x segment of LX columns; a box of width W needs
+  // W + 2(K-1) <= LX, so at K = 2 boxes wider than min(xface, 30) keep the strip
+  // march. 0: today's dispatch. Outside 0..kXfaceMax: an invalid argument before
+  // any work. plan_dispatch3d below is the rule both launchers run.
   int xface = 0;
 };
 constexpr int kXfaceMax = 32;
+
+// Which kernel path each box of a 3D launch takes (kernel_select.cpp, host only;
+// both launchers call it, so what it returns is what runs). K = 1: a box at most
+// tune.xface wide runs the x-face kernel on 8, 16 or 32 lanes per row (the
+// smallest >= its width), any other box at most 8 wide the thin-box path (one
+// thread per row), the rest the strip march. K = 2: a box at most tune.xface wide
+// with W + 2(K-1) <= 32 runs the K-step x-face kernel on the smallest lanes-per-
+// segment class LX in {8, 16, 32} with W + 2(K-1) <= LX, the rest the strip march.
+// out[i] describes boxes[i]; an empty box has path kPathNone. lanes: the lanes
+// that share one row of the box (LX; 64 for a strip; 1 for the thin path).
+// Throws on K other than 1 or 2 and on tune.xface outside 0..kXfaceMax.
+enum Path3D { kPathNone = 0, kPathMarch = 1, kPathThin = 2, kPathXface = 3 };
+struct Dispatch3D {
+  int path = kPathNone;
+  int lanes = 0;
+};
+void plan_dispatch3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning& tune,
+                     Dispatch3D* out);
+const char* path3d_name(int path);  // "none", "march", "thin", "xface"
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
 // Cells per lane both 3D launchers run: tune.vec with even nx and 16-byte
@@ -235,7 +257,8 @@ void validate_boxes(const double* T2, const double* T, int64_t nx, int64_t ny, i
 // Bitwise equal to K full-interior calls of stencil3d_boxes_* followed by a crop
 // to the boxes. T2 != T; cells outside the boxes are not written. K = 1 forwards
 // to the one-step kernel; a K that stencil3dk_has() denies is an invalid
-// argument before any work. Every box runs the strip march (no thin-box path).
+// argument before any work. Every box runs the strip march (no thin-box path)
+// unless Stencil3DTuning::xface sends it to the K-step x-face kernel.
 bool stencil3dk_has(int K);
 bool stencil3dk_has_rows(int rows);  // Stencil3DTuning::tb_rows values instantiated
 void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp, int64_t nx,

@@ -1,6 +1,7 @@
 // Host-side kernel-selection rules of the stencil launchers: which
 // pipelined (K, stages, arithmetic, cols) instantiations exist, the cells per
-// lane a launch runs, the one-step march kernel's strip width. Plain host code
+// lane a launch runs, the one-step march kernel's strip width, the path of every
+// box of a 3D launch (plan_dispatch3d). Plain host code
 // (moved out of stencil_pipe.hip / stencil.hip) so the executor's planning
 // compiles and runs without HIP, e.g. in tests/native/executor_selftest.cpp
 // under ThreadSanitizer / AddressSanitizer.
@@ -80,6 +81,45 @@ int stencil_vec(int64_t nx, const StencilTuning& tune) {
 int stencil_strip_cells(int64_t nx, const StencilTuning& tune) {
   constexpr int kWave = 64;
   return kWave * stencil_vec(nx, tune);
+}
+
+void plan_dispatch3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning& tune,
+                     Dispatch3D* out) {
+  constexpr int64_t kThinMaxWidth = 8;  // one-step boxes at most this wide: one thread per row
+  RMA_CHECK_ARG(K == 1 || K == 2, "K=" << K << " steps per pass is not instantiated (1 or 2)");
+  RMA_CHECK_ARG(tune.xface >= 0 && tune.xface <= kXfaceMax,
+                "xface=" << tune.xface << " (0: off, or the widest face box, up to "
+                         << kXfaceMax << ")");
+  RMA_CHECK_ARG(nboxes >= 0 && nboxes <= kMaxBoxes,
+                "nboxes=" << nboxes << " (at most " << kMaxBoxes << " boxes per launch)");
+  for (int i = 0; i < nboxes; ++i) {
+    const Box& b = boxes[i];
+    out[i] = Dispatch3D{};
+    if (b.empty()) continue;
+    const int64_t w = b.x1 - b.x0;
+    // columns a face segment needs: the box and, per side, the K-1 columns on
+    // which the lower levels are recomputed (none for the one-step kernel)
+    const int64_t need = w + 2 * (K - 1);
+    if (w <= tune.xface && need <= 32) {
+      out[i].path = kPathXface;
+      out[i].lanes = need <= 8 ? 8 : need <= 16 ? 16 : 32;
+    } else if (K == 1 && w <= kThinMaxWidth) {
+      out[i].path = kPathThin;
+      out[i].lanes = 1;
+    } else {
+      out[i].path = kPathMarch;
+      out[i].lanes = 64;
+    }
+  }
+}
+
+const char* path3d_name(int path) {
+  switch (path) {
+    case kPathMarch: return "march";
+    case kPathThin: return "thin";
+    case kPathXface: return "xface";
+    default: return "none";
+  }
 }
 
 }  // namespace rma

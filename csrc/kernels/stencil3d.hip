@@ -241,7 +241,9 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
   }
 }
 
-int64_t plan_boxes(BoxList& L, const Box* boxes, int nboxes, int V, int R, int chunk_z) {
+// thin[i]: boxes[i] runs the thin-box path (plan_dispatch3d's kPathThin)
+int64_t plan_boxes(BoxList& L, const Box* boxes, const bool* thin, int nboxes, int V, int R,
+                   int chunk_z) {
   L = BoxList{};
   int64_t total = 0;
   const int64_t sw = (int64_t)kWave * V;
@@ -252,7 +254,7 @@ int64_t plan_boxes(BoxList& L, const Box* boxes, int nboxes, int V, int R, int c
     L.b[n] = b;
     const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
     int64_t blocks;
-    if (b.x1 - b.x0 <= kColMaxWidth) {
+    if (thin[i]) {
       L.chunk_z[n] = -1;
       blocks = (nyb * nzb + kBlock - 1) / kBlock;
     } else {
@@ -371,11 +373,8 @@ __global__ __launch_bounds__(kBlock) void stencil3d_xface_kernel(double* __restr
   }
 }
 
-// smallest lanes-per-row class of a face box: 0, 1, 2 for LX = 8, 16, 32
-int face_class(const Box& b) {
-  const int64_t w = b.x1 - b.x0;
-  return w <= 8 ? 0 : w <= 16 ? 1 : 2;
-}
+// index of a lanes-per-row class (Dispatch3D::lanes): 0, 1, 2 for LX = 8, 16, 32
+int face_class(int lanes) { return lanes == 8 ? 0 : lanes == 16 ? 1 : 2; }
 
 int64_t plan_faces(FaceList& L, const Box* boxes, int nboxes, int LX, int chunk_z) {
   L = FaceList{};
@@ -503,32 +502,29 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   RMA_CHECK_ARG(tune.chunk_z >= 0, "chunk_z=" << tune.chunk_z);
   RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
                 "fast_math: fast7 needs lam != 0 and finite coefficients");
-  RMA_CHECK_ARG(tune.xface >= 0 && tune.xface <= kXfaceMax,
-                "xface=" << tune.xface << " (0: off, or the widest face box, up to "
-                         << kXfaceMax << ")");
+  // plan_dispatch3d (kernel_select.cpp) checks tune.xface and decides the path of
+  // every box: face boxes leave the list for the x-face kernel, the rest keep
+  // their order in the march launch (strips, or one thread per row for thin
+  // boxes). xface = 0 has no face boxes: the caller's list.
+  Dispatch3D path[kMaxBoxes];
+  plan_dispatch3d(1, boxes, nboxes, tune, path);
   hipStream_t s = as_stream(stream);
-  // xface > 0: boxes at most that wide leave the list for the x-face kernel, the
-  // rest run the march as before. xface = 0: the caller's list, today's dispatch.
   Box wide[kMaxBoxes], face[3][kMaxBoxes];
+  bool thin[kMaxBoxes];
   int nwide = 0, nface[3] = {0, 0, 0};
-  if (tune.xface > 0) {
-    for (int i = 0; i < nboxes; ++i) {
-      const Box& b = boxes[i];
-      if (b.empty()) continue;
-      if (b.x1 - b.x0 <= tune.xface) {
-        const int cls = face_class(b);
-        face[cls][nface[cls]++] = b;
-      } else {
-        wide[nwide++] = b;
-      }
+  for (int i = 0; i < nboxes; ++i) {
+    if (path[i].path == kPathXface) {
+      const int cls = face_class(path[i].lanes);
+      face[cls][nface[cls]++] = boxes[i];
+    } else if (path[i].path != kPathNone) {
+      thin[nwide] = path[i].path == kPathThin;
+      wide[nwide++] = boxes[i];
     }
-    boxes = wide;
-    nboxes = nwide;
   }
   const bool faces = nface[0] + nface[1] + nface[2] > 0;
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
-  const int64_t total = plan_boxes(L, boxes, nboxes, V, tune.rows, tune.chunk_z);
+  const int64_t total = plan_boxes(L, wide, thin, nwide, V, tune.rows, tune.chunk_z);
   if (L.n == 0 && !faces) return;
   RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
   const dim3 grid((unsigned)total);

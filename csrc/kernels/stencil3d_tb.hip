@@ -32,9 +32,9 @@
 //     and are the default. Blocks are ordered per XCD (xcd_remap) as in the
 //     one-step kernel: four waves of a block own four adjacent bands of one strip.
 //   * Odd nx or a base off 16-byte alignment runs the same march with V = 1.
-//     Every box runs the strip march (no thin-box path, and no x-face path:
-//     Stencil3DTuning::xface acts on the one-step kernel only, so the x slabs of
-//     a two-step frame keep the strip march).
+//     There is no thin-box path: every box runs the strip march, unless
+//     Stencil3DTuning::xface = W > 0 (opt-in) sends it to the x-face kernel below
+//     (boxes at most min(W, 30) wide at K = 2, the x slabs of a two-step frame).
 //
 // VGPRs / waves per SIMD at K = 2 (build's resource output; no AGPRs, no scratch):
 // (V, R) = (2, 2) 162 / 3, (2, 4) 230 / 2, (1, 2) 98 / 4, (1, 4) 132 / 3, the same
@@ -271,6 +271,270 @@ int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, in
   return total;
 }
 
+// ---------------------------------------------------------------------------
+// x-face path (Stencil3DTuning::xface): boxes narrow in x, the x slabs of a
+// frame / interior split. The strip march loads 64*V columns a row for them,
+// about nine times the cells a 14-wide slab updates. Here the same march runs
+// narrower in x and stacked in y:
+//   * A wave is RG = 64/LX groups of LX lanes (LX = 8, 16, 32). A group owns one
+//     x segment of LX columns, one cell per lane (scalar 8-byte accesses: no
+//     alignment or even-nx requirement), and a band of R output rows. It holds
+//     the R + 2K window rows of every level in registers exactly as the strip
+//     march does, Lv[K][3][NR] and ic[K][NR] on the field path, and marches along
+//     z skewed in time by level: K planes before and after a chunk, warm-up
+//     without stores. y neighbours are window rows in the lane's own registers:
+//     no cross-lane y traffic.
+//   * The band of a group is (the block's wave band) * RG + lane / LX. A group
+//     whose band is past the box is masked (it loads clamped and stores nothing);
+//     the wave leaves early only when all its groups are past the box.
+//   * x neighbours come from the adjacent lane (__shfl_up/down by 1); for level 1
+//     the first and last lane of a group take theirs from one edge load per
+//     window row (lanes i < LX/2 the column left of the segment, the others the
+//     column right of it, both clamped into the array). Level l is then valid on
+//     the lanes [l-1, LX-l] of the group, or up to an array face the segment
+//     touches: the clo / chi rule of the strip march with LX in place of 64*V.
+//   * The segment starts K-1 columns left of the box and never left of column 0;
+//     a box of width W fits when W + 2(K-1) <= LX (plan_dispatch3d picks the
+//     smallest class: at K = 2 widths up to 6, 14, 30). One face box is one
+//     segment: there is no strip loop.
+//   * A level-l cell on an array face keeps the level l-1 value. Lanes, rows and
+//     planes past the array load clamped and store masked, and what they compute
+//     feeds only masked cells: a stored level-K cell on lane i in [clo, chi] reads
+//     level l on the lanes i-(K-l) .. i+(K-l) of its own group, all inside
+//     [l-1, LX-l] or bounded by a face cell, which takes no neighbour at all; the
+//     lanes 0 and LX-1, the only ones a shuffle feeds from another group (or from
+//     a masked one), are outside that range at every level >= 2 and take the edge
+//     load at level 1. In y a lane reads only its own window rows, whose level-l
+//     rows [l, NR-l) cover what the R output rows need; rows and planes on or
+//     past a face keep the lower level, so their clamped copies are never read
+//     through. A masked group computes on clamped loads and stores nothing.
+//   * Block list as FaceList in stencil3d.hip: groups of wave bands fastest, then
+//     the z chunk. One launch per lanes-per-segment class in use, on the same
+//     stream ahead of the march of the remaining boxes. No LDS, no barrier, no
+//     atomics; all offsets 64-bit.
+//   * The same update3k expression in the same order: bitwise the strip march's
+//     cells. T2 stores follow tb_nontemporal bit 0; bit 1 (non-temporal 1/Cp
+//     loads) is not instantiated for this path, which keeps it at 48
+//     instantiations: 1/Cp loads are plain, the measured default of the march.
+//   * R follows tb_rows (2 or 4) and the planes per task tb_chunk_z; 0 takes the
+//     face path's own defaults, 2 rows and 16 planes (profiles/diffusion3d_hide.md
+//     section 4: of rows 2 / 4 x planes 16 / 32 the pair with the smallest worst
+//     case over widths 2-30 and 256^3-1024^3; 4 rows x 32 planes, the march's
+//     default, is up to 2.6x slower on a 256^3 face, which has few tasks).
+// VGPRs / waves per SIMD at K = 2 (build's resource output; no AGPRs, no scratch,
+// no LDS; the same for LX = 8, 16, 32 and both store settings):
+// canonical field R = 2: 110 / 4, R = 4: 150 / 3; canonical Uni 96 / 5, 132 / 3;
+// fast7 field 107 / 4, 149 / 3; fast7 Uni 94 / 5, 128 / 4.
+// The 48 stencil3d_tb_kernel instantiations compile to the registers, scratch and
+// occupancy listed at the top of this file, as before this path was added (the
+// launcher splits the box list on the host; the strip march is untouched).
+// ---------------------------------------------------------------------------
+constexpr int kTbFaceDefaultRows = 2;
+constexpr int64_t kTbFaceDefaultChunkZ = 16;
+
+struct FaceListK {
+  Box b[kMaxBoxes];
+  int64_t xs[kMaxBoxes];         // first column of the segment
+  int64_t bands[kMaxBoxes];      // group tasks along y: ceil(rows / R)
+  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / (RG * waves per block))
+  int64_t chunk_z[kMaxBoxes];    // output planes per task
+  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
+  int n;
+};
+
+template <int K, int LX, int R, bool NTS, bool Uni, int A>
+__global__ __launch_bounds__(kBlock) void stencil3d_tb_xface_kernel(double* __restrict__ T2,
+                                                                    const double* __restrict__ T,
+                                                                    Factor<Uni> iCp, int64_t nx,
+                                                                    int64_t ny, int64_t nz,
+                                                                    FaceListK L, Coef3<A> k) {
+  static_assert(LX == 8 || LX == 16 || LX == 32, "lanes per segment");
+  constexpr int RG = kWave / LX;  // groups of a wave
+  constexpr int NR = R + 2 * K;   // rows of the level-0 window
+  const int64_t b = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int bi = 0;
+  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
+  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const Box box = L.b[bi];
+  const int64_t plane = nx * ny;
+  // block lb of a box: the group of 4 wave bands fastest, then the z chunk
+  const int64_t wband = (lb % L.groups[bi]) * kWavesPerBlock + wave;
+  const int64_t zc = lb / L.groups[bi];
+  if (wband * RG >= L.bands[bi]) return;  // every group of the wave is past the box
+  const int lane = threadIdx.x & (kWave - 1);
+  const int i = lane % LX;
+  const int64_t band = wband * RG + lane / LX;
+  const bool live = band < L.bands[bi];  // group-uniform
+  const int64_t xs = L.xs[bi];
+  const int64_t ya = box.y0 + band * R;
+  const int64_t za = box.z0 + zc * L.chunk_z[bi];
+  const int64_t zb = min(box.z1, za + L.chunk_z[bi]);
+
+  const int64_t x = xs + i;             // the lane's column
+  const int64_t xl = min(x, nx - 1);    // clamped load column
+  const int64_t eidx = (i < LX / 2) ? max(xs - 1, (int64_t)0) : min(xs + LX, nx - 1);
+  // lanes on which level K is valid: all the way to an array face the segment touches
+  const int clo = xs == 0 ? 0 : K - 1;
+  const int chi = xs + LX >= nx ? LX - 1 : LX - K;
+  const bool m = live && x >= box.x0 && x < box.x1 && i >= clo && i <= chi;
+  const bool xface = x <= 0 || x >= nx - 1;
+  // output rows of the group inside the box (none for a masked group)
+  const int nrows = live ? (int)min((int64_t)R, box.y1 - ya) : 0;
+  int64_t row[NR];  // element offset of window row j (global row ya-K+j, clamped)
+  bool rface[NR];   // that row lies on (or past) an array face
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int64_t g = ya - K + j;
+    row[j] = min(max(g, (int64_t)0), ny - 1) * nx;
+    rface[j] = g <= 0 || g >= ny - 1;
+  }
+
+  // Lv[l][s][j]: level l, plane slot s (planes p-l-2, p-l-1, p-l when plane p of
+  // level 0 is the newest), window row j. ic[l]: 1/Cp of plane p-l-1.
+  double Lv[K][3][NR], ic[Uni ? 1 : K][Uni ? 1 : NR];
+#pragma unroll
+  for (int l = 0; l < K; ++l)
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      Lv[l][0][j] = Lv[l][1][j] = Lv[l][2][j] = 0.0;
+      if constexpr (!Uni) ic[l][j] = 0.0;
+    }
+  int64_t p = za - K + 2;
+  {
+    const double* p0 = T + min(max(p - 2, (int64_t)0), nz - 1) * plane;
+    const double* p1 = T + min(max(p - 1, (int64_t)0), nz - 1) * plane;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      Lv[0][0][j] = p0[row[j] + xl];
+      Lv[0][1][j] = p1[row[j] + xl];
+    }
+  }
+  for (; p < zb + K; ++p) {
+    const int64_t pc = min(max(p - 1, (int64_t)0), nz - 1);  // centre plane of level 1
+    const double* pf = T + min(max(p, (int64_t)0), nz - 1) * plane;
+    double ed[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) Lv[0][2][j] = pf[row[j] + xl];
+#pragma unroll
+    for (int j = 1; j < NR - 1; ++j) {
+      if constexpr (!Uni) ic[0][j] = iCp[pc * plane + row[j] + xl];
+      ed[j] = T[pc * plane + row[j] + eidx];
+    }
+#pragma unroll
+    for (int l = 1; l <= K; ++l) {
+      const int64_t z = p - l;  // plane this level computes
+      if (l == K && z < za) continue;  // warm-up: nothing to store yet
+      const bool zface = z <= 0 || z >= nz - 1;
+#pragma unroll
+      for (int j = l; j < NR - l; ++j) {
+        const double cu = Lv[l - 1][1][j];
+        double left = __shfl_up(cu, 1);
+        double right = __shfl_down(cu, 1);
+        if (l == 1) {
+          if (i == 0) left = ed[j];
+          if (i == LX - 1) right = ed[j];
+        }
+        double f;
+        if constexpr (Uni) f = iCp; else f = ic[l - 1][j];
+        const double res = update3k<A, Uni>(left, cu, right, Lv[l - 1][1][j - 1],
+                                            Lv[l - 1][1][j + 1], Lv[l - 1][0][j],
+                                            Lv[l - 1][2][j], f, k);
+        if (l < K) {
+          Lv[l < K ? l : 0][2][j] = (zface || rface[j] || xface) ? cu : res;
+        } else if (m && j - K < nrows) {
+          double* q = T2 + z * plane + row[j] + x;
+          if constexpr (NTS) {
+            __builtin_nontemporal_store(res, q);
+          } else {
+            *q = res;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < K; ++l)
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        Lv[l][0][j] = Lv[l][1][j];
+        Lv[l][1][j] = Lv[l][2][j];
+      }
+    if constexpr (!Uni) {
+#pragma unroll
+      for (int l = K - 1; l > 0; --l)
+#pragma unroll
+        for (int j = 0; j < NR; ++j) ic[l][j] = ic[l - 1][j];
+    }
+  }
+}
+
+int64_t plan_faces_k(FaceListK& L, const Box* boxes, int nboxes, int K, int LX, int R,
+                     int chunk_z) {
+  L = FaceListK{};
+  int64_t total = 0;
+  const int64_t rg = kWave / LX;
+  for (int i = 0; i < nboxes; ++i) {
+    const Box& b = boxes[i];
+    const int n = L.n++;
+    L.b[n] = b;
+    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
+    // the segment starts K-1 columns left of the box (its first valid lane) and
+    // never left of the array (valid from the face on there)
+    L.xs[n] = std::max<int64_t>(b.x0 - (K - 1), 0);
+    L.bands[n] = (nyb + R - 1) / R;
+    const int64_t wbands = (L.bands[n] + rg - 1) / rg;
+    L.groups[n] = (wbands + kWavesPerBlock - 1) / kWavesPerBlock;
+    // each chunk re-reads 2K planes and recomputes K-1
+    L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : kTbFaceDefaultChunkZ, nzb);
+    total += L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
+    L.block_end[n] = total;
+  }
+  return total;
+}
+
+template <int K, int LX, int R, int A>
+void launch_face_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
+                    const double* iCp, int64_t nx, int64_t ny, int64_t nz, const FaceListK& L,
+                    const Coef3<A>& c, bool uni, double fac) {
+  const dim3 block(kBlock);
+  if (uni) {
+    if (nt & 1)
+      stencil3d_tb_xface_kernel<K, LX, R, true, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+                                                                               nz, L, c);
+    else
+      stencil3d_tb_xface_kernel<K, LX, R, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
+                                                                                nz, L, c);
+  } else if (nt & 1) {
+    stencil3d_tb_xface_kernel<K, LX, R, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny,
+                                                                              nz, L, c);
+  } else {
+    stencil3d_tb_xface_kernel<K, LX, R, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny,
+                                                                               nz, L, c);
+  }
+}
+
+// the face boxes of one launch, one kernel launch per lanes-per-segment class in use
+template <int K, int A>
+void launch_faces_k(const Box (&face)[3][kMaxBoxes], const int (&nface)[3], int R, int chunk_z,
+                    hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
+                    int64_t nx, int64_t ny, int64_t nz, const Coef3<A>& c, bool uni, double fac) {
+  for (int cls = 0; cls < 3; ++cls) {
+    if (!nface[cls]) continue;
+    FaceListK L{};
+    const int64_t total = plan_faces_k(L, face[cls], nface[cls], K, 8 << cls, R, chunk_z);
+    RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
+    const dim3 grid((unsigned)total);
+#define RMA_TB_FACE(LX)                                                                         \
+  (R == 2 ? launch_face_nt<K, LX, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, uni, fac)    \
+          : launch_face_nt<K, LX, 4, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, uni, fac))
+    if (cls == 0) RMA_TB_FACE(8);
+    else if (cls == 1) RMA_TB_FACE(16);
+    else RMA_TB_FACE(32);
+#undef RMA_TB_FACE
+    RMA_HIP_LAUNCH_CHECK();
+  }
+}
+
 template <int K, int V, int R, int A>
 void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
                int64_t nx, int64_t ny, int64_t nz, const BoxListK& L, const Coef3<A>& c,
@@ -340,19 +604,46 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
   RMA_CHECK_ARG(tune.tb_chunk_z >= 0, "tb_chunk_z=" << tune.tb_chunk_z);
   RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
                 "fast_math: fast7 needs lam != 0 and finite coefficients");
+  // plan_dispatch3d (kernel_select.cpp) checks tune.xface and decides the path of
+  // every box: face boxes leave the list for the x-face kernel, launched first on
+  // the same stream, the rest keep their order in the strip march. xface = 0 has
+  // no face boxes: the caller's list, launch for launch.
+  Dispatch3D path[kMaxBoxes];
+  plan_dispatch3d(K, boxes, nboxes, tune, path);
+  Box wide[kMaxBoxes], face[3][kMaxBoxes];
+  int nwide = 0, nface[3] = {0, 0, 0};
+  for (int i = 0; i < nboxes; ++i) {
+    if (path[i].path == kPathXface) {
+      const int cls = path[i].lanes == 8 ? 0 : path[i].lanes == 16 ? 1 : 2;
+      face[cls][nface[cls]++] = boxes[i];
+    } else if (path[i].path != kPathNone) {
+      wide[nwide++] = boxes[i];
+    }
+  }
+  const bool faces = nface[0] + nface[1] + nface[2] > 0;
+  const int Rf = tune.tb_rows > 0 ? tune.tb_rows : kTbFaceDefaultRows;
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxListK L{};
-  const int64_t total = plan_boxes_k(L, boxes, nboxes, K, V, R, tune.tb_chunk_z);
-  if (L.n == 0) return;
+  const int64_t total = plan_boxes_k(L, wide, nwide, K, V, R, tune.tb_chunk_z);
+  if (L.n == 0 && !faces) return;
   RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
+  hipStream_t s = as_stream(stream);
   if (tune.fast_math) {  // the uniform variant takes g = gs * value, formed here
     const Fast7 f = fast7_constants(c);
-    launch_k<2, kFast7>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal, T2, T,
-                        iCp, nx, ny, nz, L, f, tune.xcd_remap ? 1 : 0, tune.uniform,
-                        f.gs * tune.uniform_value);
+    const double g = f.gs * tune.uniform_value;
+    if (faces)
+      launch_faces_k<2, kFast7>(face, nface, Rf, tune.tb_chunk_z, s, tune.tb_nontemporal, T2, T,
+                                iCp, nx, ny, nz, f, tune.uniform, g);
+    if (L.n == 0) return;
+    launch_k<2, kFast7>(V, R, dim3((unsigned)total), s, tune.tb_nontemporal, T2, T, iCp, nx, ny,
+                        nz, L, f, tune.xcd_remap ? 1 : 0, tune.uniform, g);
   } else {
-    launch_k<2, kCanonical3>(V, R, dim3((unsigned)total), as_stream(stream), tune.tb_nontemporal,
-                             T2, T, iCp, nx, ny, nz, L, c, tune.xcd_remap ? 1 : 0, tune.uniform,
+    if (faces)
+      launch_faces_k<2, kCanonical3>(face, nface, Rf, tune.tb_chunk_z, s, tune.tb_nontemporal, T2,
+                                     T, iCp, nx, ny, nz, c, tune.uniform, tune.uniform_value);
+    if (L.n == 0) return;
+    launch_k<2, kCanonical3>(V, R, dim3((unsigned)total), s, tune.tb_nontemporal, T2, T, iCp, nx,
+                             ny, nz, L, c, tune.xcd_remap ? 1 : 0, tune.uniform,
                              tune.uniform_value);
   }
   RMA_HIP_LAUNCH_CHECK();

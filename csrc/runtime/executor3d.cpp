@@ -169,7 +169,7 @@ void Diffusion3DExecutor::launch(int K, const Box* boxes, int n, bool frame, dou
   tn.fast_math = p_.fast_math ? 1 : 0;
   tn.uniform = uniform_;
   tn.uniform_value = uniform_ ? c0_ : 0.0;
-  tn.xface = (K == 1 && frame) ? xface_ : 0;
+  tn.xface = frame ? xface_ : 0;  // one- and two-step frames (plan_dispatch3d caps the width)
   if (K == 1)
     stencil3d_boxes_gpu(Tout, Tin, iCp_, nx_, ny_, nz_, b, m, p_.coef, tn, s);
   else

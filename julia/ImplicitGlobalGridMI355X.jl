@@ -277,8 +277,9 @@ mutable struct Diffusion3DExecutor
 end
 
 # steps_per_pass = 1 or 2; b_width = perf_hide's boundary width per dimension from the
-# array edge; xface = 0..32 (the widest frame box on the one-step kernel's x-face path,
-# -1: min(max(b_width[1], overlap_x), 32)). T2 must hold a copy of T.
+# array edge; xface = 0..32 (the widest frame box on the x-face path of the one- and
+# two-step kernels, two-step frames up to width 30; -1: min(max(b_width[1], overlap_x), 32)).
+# T2 must hold a copy of T.
 function Diffusion3DExecutor(T, T2, iCp, coef::NTuple{5,Float64}; mode::Integer=1,
                              steps_per_pass::Integer=1, b_width=(16, 2, 2),
                              fast_math::Bool=false, xface::Integer=0)

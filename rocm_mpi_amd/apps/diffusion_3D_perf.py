@@ -35,8 +35,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--b-width", dest="b_width", type=_triple, default=(16, 2, 2),
                     help="perf_hide boundary width a,b,c in cells from the array edge")
     ap.add_argument("--xface", type=int, default=0,
-                    help="perf_hide: widest frame box on the one-step kernel's x-face path "
-                         "(0: off, -1: the x boundary width)")
+                    help="perf_hide: widest frame box on the kernels' x-face path, one- and "
+                         "two-step passes (0: off, -1: the x boundary width)")
     ap.add_argument("--device", default=None, help="cpu, cuda, cuda:N (default: one GPU per rank)")
     ap.add_argument("--transport", default=os.environ.get("RMA_TRANSPORT", "auto"),
                     choices=["auto", "rccl", "ipc", "staged", "gloo", "self"])
@@ -87,6 +87,40 @@ def factor_line(model) -> str:
             f"{why}")
 
 
+def face_path_text(model, k: int, frame) -> str:
+    """Which frame boxes of a k-step pass run the x-face path, as the launcher
+    decides it (ops.stencil3d_dispatch): their widths and lanes per row, and for
+    the x slabs that stay on the strip march, why."""
+    from .. import ops
+    from .._native import has_native
+
+    xf = model.frame_xface(k)
+    if not xf:
+        return "no box on the x-face path (--xface 0)"
+    if not has_native():
+        return f"x-face width {xf} (the native extension decides per box; it is not built)"
+    cfg = model.cfg
+    plan = ops.stencil3d_dispatch(k, (cfg.nz, cfg.ny, cfg.nx), frame,
+                                  ops.Stencil3DTuning(xface=xf))
+    faced = [(b[1] - b[0], lanes) for b, path, lanes in plan if path == "xface"]
+    if faced:
+        boxes = ", ".join(f"width {w} on {lanes} lanes per row" for w, lanes in sorted(set(faced)))
+        text = f"x-face path for {len(faced)} of {len(frame)} frame boxes ({boxes}; width <= {xf})"
+    else:
+        text = f"no box on the x-face path (width <= {xf})"
+    cap = ops.XFACE_MAX - 2 * (k - 1)  # a k-step segment needs width + 2(k-1) <= 32 columns
+    # the x slabs are the frame boxes that do not span the owned x range
+    own = model.owned_box(k)
+    kept = [b[1] - b[0] for b, path, _ in plan
+            if path != "xface" and (b[0], b[1]) != (own[0], own[1])]
+    if kept:
+        why = [f"width {w} > " + (f"--xface {xf}" if w > xf else
+                                  f"{cap}, the widest box of the {k}-step face path")
+               for w in sorted(set(kept))]
+        text += f"; x slabs on the march: {', '.join(why)}"
+    return text
+
+
 def hide_line(model) -> str:
     """The frame / interior split of the perf_hide passes (rank 0's boxes)."""
     cfg = model.cfg
@@ -96,11 +130,7 @@ def hide_line(model) -> str:
         own = model.owned_box(k)
         vol = lambda b: (b[1] - b[0]) * (b[3] - b[2]) * (b[5] - b[4])  # noqa: E731
         share = sum(vol(b) for b in frame) / max(1, vol(own))
-        xf = model.frame_xface() if k == 1 else 0
-        faced = [b for b in frame if b[1] - b[0] <= xf]
-        path = (f"x-face path for {len(faced)} of {len(frame)} frame boxes (width <= {xf})"
-                if faced else "no box on the x-face path"
-                + (" (the two-step kernel has none)" if k > 1 else " (--xface 0)" if not xf else ""))
+        path = face_path_text(model, k, frame)
         overlap = ("frame + exchange overlap the interior" if frame and inner is not None
                    and model.device.type == "cuda" else
                    "boxes in sequence: frame, exchange, interior" if frame and inner is not None

@@ -75,9 +75,11 @@ one launch on the current stream followed by the exchange, as ``perf``. CPU
 tensors run the same boxes in sequence: frame, exchange, interior.
 ``temporal``, ``fast_math`` and the uniform-factor scan apply as for ``perf``.
 ``xface`` (default 0, decided by profiles/diffusion3d_hide.md): the width up to
-which the frame's boxes run the one-step kernel's x-face path
+which the frame's boxes run the kernels' x-face paths
 (``Stencil3DTuning.xface``); ``None`` takes ``min(max(b_width[0], overlap), 32)``.
-Two-step passes never use it: the two-step kernel has no such path.
+It applies to the frame launch of one- and two-step passes alike; in a two-step
+pass a box needs two more columns than its width, so boxes wider than 30 keep
+the strip march (``ops.stencil3d_dispatch`` tells which box runs where).
 
 ``native`` (off by default; perf and perf_hide on a GPU whose grid has a native
 halo engine: the self, rccl, ipc and loopback transports): ``step(n)`` is one call
@@ -145,8 +147,8 @@ class Diffusion3DConfig:
     uniform_factor: bool = True  # uniform-1/Cp kernel variants where 1/Cp is one value
     fast_math: bool = False  # the fast7 arithmetic in every pass, perf / perf_hide only
     b_width: tuple = (16, 2, 2)  # perf_hide boundary width per dimension, from the array edge
-    # perf_hide: widest frame box on the one-step kernel's x-face path (0: off,
-    # None: min(max(b_width[0], overlap), 32)); profiles/diffusion3d_hide.md
+    # perf_hide: widest frame box on the x-face path of the one- and two-step kernels
+    # (0: off, None: min(max(b_width[0], overlap), 32)); profiles/diffusion3d_hide.md
     xface: int | None = 0
     # perf / perf_hide on a GPU with a native halo engine: step(n) is enqueued by the
     # C++ time loop (_C.Executor3D, csrc/runtime/executor3d.cpp) instead of pass by
@@ -401,8 +403,13 @@ class Diffusion3D:
         return ops.hide_boxes3d((self.cfg.nx, self.cfg.ny, self.cfg.nz), self.owned_box(k),
                                 sides, g.overlaps, self.cfg.b_width)
 
-    def frame_xface(self) -> int:
-        """Stencil3DTuning.xface of the frame launch of a one-step perf_hide pass."""
+    def frame_xface(self, k: int = 1) -> int:
+        """Stencil3DTuning.xface of the frame launch of a k-step perf_hide pass:
+        cfg.xface, or with None ``min(max(b_width[0], overlap), 32)``. The value
+        does not depend on k; what it does per box does (``ops.stencil3d_dispatch``:
+        a two-step pass keeps boxes wider than 30 on the strip march)."""
+        if int(k) not in ops.TEMPORAL_3D:
+            raise ValueError(f"k={k} steps per pass (one of {ops.TEMPORAL_3D})")
         xf = self.cfg.xface
         if xf is None:
             xf = min(max(int(self.cfg.b_width[0]), int(self.g.overlaps[0])), ops.XFACE_MAX)
@@ -411,9 +418,9 @@ class Diffusion3D:
     def _launch(self, k: int, boxes, frame: bool = False) -> None:
         """One k-step launch T -> T2 on the boxes, on the current stream."""
         tn = self._tuning(k)
+        if frame and self.frame_xface(k):
+            tn = dataclasses.replace(tn or ops.Stencil3DTuning(), xface=self.frame_xface(k))
         if k == 1:
-            if frame and self.frame_xface():
-                tn = dataclasses.replace(tn or ops.Stencil3DTuning(), xface=self.frame_xface())
             ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, boxes, tuning=tn)
         else:
             ops.stencil3dk_step(k, self.T2, self.T, self.iCp, self.coef, boxes, tuning=tn)

@@ -70,12 +70,15 @@ class Stencil3DTuning:
     the fast7 C++ twin, bitwise equal to the GPU kernels. It needs the native
     extension and a coefficient set that passes ``fast7_ok``.
 
-    ``xface`` (one-step kernel only, 0..32, default 0 = today's dispatch): the
-    widest box in x that runs the x-face path of csrc/kernels/stencil3d.hip, a
-    wave of 64/LX rows of LX = 8, 16 or 32 lanes marching along z, instead of the
-    thin-box path (widths up to 8) or the 128-cell strip march. Bitwise the same
-    result. CPU tensors accept and ignore it; the two-step kernel does not have
-    the path."""
+    ``xface`` (0..32, default 0 = today's dispatch): the widest box in x that runs
+    an x-face path instead of the thin-box path (one-step, widths up to 8) or the
+    128-cell strip march. One-step kernel (csrc/kernels/stencil3d.hip): a wave of
+    64/LX rows of LX = 8, 16 or 32 lanes marching along z. Two-step kernel
+    (csrc/kernels/stencil3d_tb.hip): a wave of 64/LX groups of LX lanes, each the
+    two-step march of one LX-column segment; a box of width W needs W + 2 <= LX,
+    so boxes wider than ``min(xface, 30)`` keep the strip march. Bitwise the same
+    result. ``stencil3d_dispatch`` tells which box takes which path. CPU tensors
+    accept and ignore it."""
 
     rows: int = 4
     unroll: int = 2
@@ -295,13 +298,19 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
     cropped to the boxes; cells outside the boxes keep T2's values.
     ``tuning.uniform`` as in ``stencil3d_step``: the GPU kernel does not read
     ``iCp`` then; accepted and ignored on CPU tensors. ``tuning.fast_math``: every
-    level in the fast7 arithmetic (K = 1 included), on GPU and CPU tensors alike."""
+    level in the fast7 arithmetic (K = 1 included), on GPU and CPU tensors alike.
+    ``tuning.xface`` sends boxes at most ``min(xface, 30)`` wide in x through the
+    two-step kernel's x-face path (bitwise the same cells; ``stencil3d_dispatch``);
+    CPU tensors accept and ignore it."""
     K = int(K)
     if K not in TEMPORAL_3D:
         raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
     if K == 1:
         stencil3d_step(T2, T, iCp, coef, boxes, tuning)
         return
+    xface = int(tuning.xface) if tuning is not None else 0
+    if not 0 <= xface <= XFACE_MAX:
+        raise ValueError(f"xface={xface} (0: off, or the widest face box, up to {XFACE_MAX})")
     check_field("T", T)
     if T.dim() != 3:
         raise ValueError(f"T must be a (nz, ny, nx) field, got shape {tuple(T.shape)}")
@@ -325,13 +334,34 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
                                   int(tn.nontemporal), int(tn.chunk_z), int(tn.xcd_remap),
                                   int(tn.tb_rows), int(tn.tb_chunk_z), int(tn.tb_nontemporal),
                                   stream_handle(T), True, *_uniform_args(tn, iCp),
-                                  fast_math=fast)
+                                  fast_math=fast, xface=xface)
     elif has_native():
         native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
                                   tuple(coef), 4, 1, 2, 0, 0, 0, 0, 0, 0, 0, False,
                                   fast_math=fast)
     else:
         stencil3dk_torch(K, T2, T, iCp, coef, boxes)
+
+
+def stencil3d_dispatch(K: int, shape: Sequence[int], boxes: Sequence[Box],
+                       tuning: Stencil3DTuning | None = None) -> list:
+    """The kernel path each non-empty box of a K-step GPU launch on a
+    ``(nz, ny, nx)`` field takes: ``[(box, path, lanes), ...]`` in the order of
+    ``boxes``, ``path`` one of ``"march"`` (the strip march, 64 lanes a strip),
+    ``"thin"`` (one-step boxes at most 8 wide, one thread per row, ``lanes`` 1)
+    and ``"xface"`` (``tuning.xface``: ``lanes`` = 8, 16 or 32 per row). It is the
+    host function both launchers run (``plan_dispatch3d``, csrc/kernels/
+    kernel_select.cpp), so it needs the native extension and no GPU."""
+    K = int(K)
+    if K not in TEMPORAL_3D:
+        raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
+    xface = int(tuning.xface) if tuning is not None else 0
+    if not 0 <= xface <= XFACE_MAX:
+        raise ValueError(f"xface={xface} (0: off, or the widest face box, up to {XFACE_MAX})")
+    nz, ny, nx = (int(v) for v in shape)
+    boxes = validate_boxes(boxes, nx, ny, nz)
+    got = native().stencil3d_dispatch(K, boxes, xface)
+    return [(b, path, int(lanes)) for b, (path, lanes) in zip(boxes, got)]
 
 
 def stencil3dk_torch(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor,
