@@ -48,17 +48,21 @@ def step3(T, iCp, mlam, rdx, rdy, rdz, dt):
 
 
 def run3(nxg, nyg, nzg, nt, lx=10.0, ly=10.0, lz=10.0, lam=1.0, Cp0=1.0, T0=None,
-         periods=(0, 0, 0)):
+         periods=(0, 0, 0), iCp=None):
     """nt steps on the (nzg, nyg, nxg) array of the global grid.
 
     On a periodic dimension the array's first and last cells are ghosts of the
     cells one period away, so the grid has n - 2 distinct cells there (that is
     ImplicitGlobalGrid's n_g, which sets the spacing) and the ghosts are
-    refreshed after every step, as a halo update does."""
+    refreshed after every step, as a halo update does.
+
+    ``iCp``: a (nzg, nyg, nxg) array of 1/Cp (ghosts included) instead of the
+    constant 1/Cp0; dt keeps Cp0, as the model's does."""
     ng = [n - 2 if p else n for n, p in zip((nxg, nyg, nzg), periods)]
     dx, dy, dz, dt = params3(*ng, lx, ly, lz, lam, Cp0)
     T = initial3(nxg, nyg, nzg, lx, ly, lz) if T0 is None else np.array(T0, dtype=np.float64)
-    iCp = np.full_like(T, 1.0 / Cp0)
+    iCp = np.full_like(T, 1.0 / Cp0) if iCp is None else np.array(iCp, dtype=np.float64)
+    assert iCp.shape == T.shape
     for _ in range(nt):
         T = step3(T, iCp, -lam, 1.0 / dx, 1.0 / dy, 1.0 / dz, dt)
         for ax, per in zip((2, 1, 0), periods):
@@ -102,6 +106,27 @@ def random_field3(nx, ny, nz, geom, seed, lo=0.0, hi=1.0):
                 idx = ((gz * geom.nyg + gy) * geom.nxg + gx) % M64
                 out[iz, iy, ix] = lo + (hi - lo) * uniform01(seed % M64, idx)
     return out
+
+
+def random_field3_np(nx, ny, nz, geom, seed, lo=0.0, hi=1.0):
+    """random_field3 for grids too large for its Python loop: the same integers
+    in NumPy uint64 arrays, whose products and sums wrap mod 2**64."""
+    u64 = np.uint64
+
+    def axis(g0, n, ng, periodic):
+        g = g0 + np.arange(n, dtype=np.int64)
+        return ((g - 1) % ng if periodic else g).astype(u64)
+
+    gx = axis(geom.gx0, nx, geom.nxg, geom.periodx)
+    gy = axis(geom.gy0, ny, geom.nyg, geom.periody)
+    gz = axis(geom.gz0, nz, geom.nzg, geom.periodz)
+    idx = (gz[:, None, None] * u64(geom.nyg) + gy[None, :, None]) * u64(geom.nxg) \
+        + gx[None, None, :]
+    z = (idx + u64(1)) * u64(GOLDEN) + u64(seed % M64)
+    z = (z ^ (z >> u64(30))) * u64(MIX1)
+    z = (z ^ (z >> u64(27))) * u64(MIX2)
+    z = z ^ (z >> u64(31))
+    return lo + (hi - lo) * ((z >> u64(11)).astype(np.float64) * 2.0**-53)
 
 
 # ---------------------------------------------------------------------------
