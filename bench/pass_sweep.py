@@ -71,6 +71,11 @@ def main(argv=None):
                     help="depths timed like --exec-uniform but at six cells per lane (K = 17..24; "
                          "rows kernel='exec_uni6'): the A/B of profiles/r8/six_cells.md. Rows "
                          "per task other than the executor's: --kinds exec_uni6:K:rows")
+    ap.add_argument("--graded", default="",
+                    help="K:r0/r1/r2[/fill],...: the six-cell uniform pass with graded task rows "
+                         "(row bands of r0 > r1 > r2 rows per task, native plan_row_bands sized "
+                         "from the device's resident blocks; rows kernel='graded6'): the A/B of "
+                         "profiles/r9/graded_rows.md")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
 
@@ -138,6 +143,9 @@ def main(argv=None):
     for item in filter(None, a.kinds.split(",")):
         k, K, *c = item.split(":")  # kernel:K[:chunk_rows]
         cfgs.append((k, int(K), 0, int(c[0])) if c else (k, int(K), 0))
+    for item in filter(None, a.graded.split(",")):
+        K, spec = item.split(":")
+        cfgs.append(("graded6", int(K), 0, spec))
     for item in filter(None, a.chunks5.split(",")):
         K, cs = item.split(":")
         for c in cs.split("/"):
@@ -147,7 +155,21 @@ def main(argv=None):
         for c in cs.split("/"):
             cfgs.append(("pipe2", int(K), 0, int(c)))
 
-    EXEC = ("exec", "exec_uni", "exec_uni6")
+    EXEC = ("exec", "exec_uni", "exec_uni6", "graded6")
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    band_cache: dict = {}
+
+    def graded_bands(K, spec, kid, ch):
+        # the executor's bands for this tile (launch_region): (rects, rows per task)
+        if (K, spec) not in band_cache:
+            forced, _, rows, fill = N.parse_task_rows(spec)
+            assert forced, spec
+            occ = N.stencil_pipe_occupancy(K, N.pipe_default_stages(K), kid - 9, 6)[0]
+            bands = N.plan_row_bands(1, n - 1, N.pipe_strip_count(1, n - 1, K, 6),
+                                     cus * max(1, occ), rows, ch, fill)
+            band_cache[(K, spec)] = ([(1, n - 1, y0, y1) for y0, y1, _ in bands],
+                                     [r for _, _, r in bands])
+        return band_cache[(K, spec)]
     rect = [ops.interior_rect(n, n)]
     names = {v: k for k, v in {**ops.KERNELS, **ops.LAB_KERNELS}.items()}
     # every configuration at every coefficient grid: (spec, kind, K, S[, chunk])
@@ -159,6 +181,12 @@ def main(argv=None):
             ops.stencil_step(T2, T, iCp, coef, rect, ops.StencilTuning())
         elif kind == "two_step":
             ops.stencil2_step(T2, T, iCp, coef, rect, ops.StencilTuning(chunk_rows=16, unroll=2))
+        elif kind == "graded6":
+            kid, vec, ch = N.fast_kernel_k(K, n, tuple(coef))
+            rects, rows = graded_bands(K, c, kid, ch)
+            N.stencilk_rects(K, T2.data_ptr(), T.data_ptr(), iCp.data_ptr(), n, n, rects,
+                             tuple(coef), ch, 3, ops.stream_handle(T), True, 1, 6, kid, 0, 0,
+                             True, 1.0, rows, len(rects))
         elif kind in EXEC:
             kid, vec, ch = N.fast_kernel_k(K, n, tuple(coef))
             tn = ops.StencilTuning(chunk_rows=c or ch, kernel=names[kid],
@@ -211,6 +239,9 @@ def main(argv=None):
                      "ms_per_pass": round(med, 3), "ms_min": round(min(times[(cs,) + c]), 3),
                      "ms_per_step": round(med / K, 4), "rel": round(med / base, 4),
                      "teff_equiv_GBps": round(K * 24 * n * n / 1e9 / (med / 1e3), 1)})
+    for (K, spec), (rects, rws) in band_cache.items():
+        print(f"[pass_sweep] graded6 K={K} {spec}: bands "
+              f"{[(y0, y1, r) for (_, _, y0, y1), r in zip(rects, rws)]}", flush=True)
     doc = {"tile": n, "rounds": a.rounds, "one_step_ms": round(base, 3), "rows": rows,
            "note": "rel = pass time / one-step march kernel time (the planner's cost unit)"}
     s = json.dumps(doc, indent=1)

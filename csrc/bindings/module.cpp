@@ -178,9 +178,13 @@ PYBIND11_MODULE(_C, m) {
       [](int K, uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny,
          const std::vector<Rect4>& rects, const Coef4& coef, int chunk_rows, int nontemporal,
          uintptr_t stream, bool gpu, int xcd_remap, int vec, int kernel, int stages, int cols,
-         bool uniform, double uniform_value) {
+         bool uniform, double uniform_value, const std::vector<int>& rect_rows, int bands) {
         auto r = to_rects(rects);
         StencilTuning tn;
+        if (!rect_rows.empty() && rect_rows.size() != r.size())
+          throw std::invalid_argument("rect_rows: one entry per rect");
+        tn.rect_rows = rect_rows.empty() ? nullptr : rect_rows.data();
+        tn.bands = bands;
         tn.cols = cols;
         tn.uniform = uniform;
         tn.uniform_value = uniform_value;
@@ -209,7 +213,8 @@ PYBIND11_MODULE(_C, m) {
       py::arg("rects"), py::arg("coef"), py::arg("chunk_rows") = 16, py::arg("nontemporal") = 3,
       py::arg("stream") = 0, py::arg("gpu") = true, py::arg("xcd_remap") = -1,
       py::arg("vec") = 2, py::arg("kernel") = 0, py::arg("stages") = 0, py::arg("cols") = 0,
-      py::arg("uniform") = false, py::arg("uniform_value") = 0.0);
+      py::arg("uniform") = false, py::arg("uniform_value") = 0.0,
+      py::arg("rect_rows") = std::vector<int>{}, py::arg("bands") = 0);
   m.def(
       "stencil3d_boxes",
       [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
@@ -653,6 +658,64 @@ PYBIND11_MODULE(_C, m) {
   m.def("pipe_uniform_cells", &pipe_uniform_cells, py::arg("K"), py::arg("cells"));
   m.def("default_pass_costs", &default_pass_costs, py::arg("kmax"), py::arg("fast5"),
         py::arg("cells") = 0.0);
+  m.def(
+      "plan_row_bands",
+      [](int64_t y0, int64_t y1, int64_t strips, int64_t slots, const std::array<int, 3>& rows,
+         int uniform_rows, double fill) {
+        std::vector<std::tuple<int64_t, int64_t, int>> out;
+        for (const RowBand& b : plan_row_bands(y0, y1, strips, slots, rows, uniform_rows, fill))
+          out.emplace_back(b.y0, b.y1, b.rows);
+        return out;
+      },
+      py::arg("y0"), py::arg("y1"), py::arg("strips"), py::arg("slots"), py::arg("rows"),
+      py::arg("uniform_rows"), py::arg("fill") = kBandFill);
+  m.def("pipe_band_rows", &pipe_band_rows, py::arg("K"), py::arg("ny"));
+  m.def("pipe_strip_count", &pipe_strip_count, py::arg("x0"), py::arg("x1"), py::arg("K"),
+        py::arg("V"));
+  m.def(
+      "parse_task_rows",
+      [](const std::string& spec) {
+        std::array<int, 3> rows{{0, 0, 0}};
+        double fill = kBandFill;
+        bool uniform = false;
+        const bool forced = parse_task_rows(spec, rows, fill, uniform);
+        return std::make_tuple(forced, uniform, rows, fill);
+      },
+      py::arg("spec"));
+  m.def(
+      "pipe_task_map",
+      [](const std::vector<Rect4>& rects, int V, int chunk_rows, int halo, int64_t sw_block,
+         const std::vector<int>& rect_rows, int bands, int sig_rects, int remap) {
+        auto r = to_rects(rects);
+        if (!rect_rows.empty() && rect_rows.size() != r.size())
+          throw std::invalid_argument("rect_rows: one entry per rect");
+        const int* rr = rect_rows.empty() ? nullptr : rect_rows.data();
+        const int64_t n = pipe_task_map(r.data(), (int)r.size(), V, chunk_rows, halo, sw_block, rr,
+                                        bands, sig_rects, remap, nullptr);
+        std::vector<int64_t> flat((size_t)(3 * n));
+        pipe_task_map(r.data(), (int)r.size(), V, chunk_rows, halo, sw_block, rr, bands,
+                      sig_rects, remap, flat.data());
+        std::vector<std::tuple<int64_t, int64_t, int64_t>> out;
+        for (int64_t b = 0; b < n; ++b)
+          out.emplace_back(flat[3 * b], flat[3 * b + 1], flat[3 * b + 2]);
+        return out;
+      },
+      py::arg("rects"), py::arg("V"), py::arg("chunk_rows"), py::arg("halo"),
+      py::arg("sw_block") = 0, py::arg("rect_rows") = std::vector<int>{}, py::arg("bands") = 0,
+      py::arg("sig_rects") = 0, py::arg("remap") = 1);
+  m.def("pipe_last_launch", []() {
+    int64_t v[2] = {0, 0};
+    pipe_last_launch(v);
+    return std::make_tuple(v[0], v[1]);
+  });
+  m.def(
+      "stencil_pipe_occupancy",
+      [](int K, int stages, int arith, int V) {
+        int occ[2] = {0, 0};
+        stencil_pipe_occupancy(K, stages, arith, V, occ);
+        return std::make_tuple(occ[0], occ[1]);
+      },
+      py::arg("K"), py::arg("stages"), py::arg("arith"), py::arg("V"));
   m.def("pipe_default_stages", &pipe_default_stages, py::arg("K"));
   m.def("pipe_default_cols", &pipe_default_cols, py::arg("K"), py::arg("stages"),
         py::arg("arith") = 0);
@@ -744,6 +807,16 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("steps_done", &DiffusionExecutor::steps_done)
       .def_property_readonly("passes_done", &DiffusionExecutor::passes_done)
       .def_property_readonly("fused_passes", &DiffusionExecutor::fused_passes)
+      .def_property_readonly("graded_passes", &DiffusionExecutor::graded_passes)
+      .def(
+          "row_bands",
+          [](DiffusionExecutor& e, int K, const Rect4& r) {
+            std::vector<std::tuple<int64_t, int64_t, int>> out;
+            for (const RowBand& b : e.row_bands(K, to_rects({r})[0]))
+              out.emplace_back(b.y0, b.y1, b.rows);
+            return out;
+          },
+          py::arg("K"), py::arg("rect"))
       .def_property_readonly("uniform_factor", &DiffusionExecutor::uniform_factor)
       .def("rescan_factor", &DiffusionExecutor::rescan_factor,
            py::call_guard<py::gil_scoped_release>())

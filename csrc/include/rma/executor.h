@@ -118,6 +118,11 @@ class DiffusionExecutor {
   int64_t passes_done() const { return passes_; }
   // passes enqueued as frame-first fused launches (RMA_EXEC_FUSED)
   int64_t fused_passes() const { return fused_passes_; }
+  // passes launched with graded task rows (more than one row band, launch_region)
+  int64_t graded_passes() const { return graded_passes_; }
+  // the row bands (y0, y1, rows per task) launch_region gives a pass of depth K
+  // over `r` with the tuning pass_tuning(K, 0); one band: uniform rows
+  std::vector<RowBand> row_bands(int K, const Rect& r);
   // throws if a fused pass's bounded wait for its frame flag timed out (the
   // halos of that pass are wrong); also checked at every run() and timings()
   void check_error() const { check_fused_error(); }
@@ -183,6 +188,23 @@ class DiffusionExecutor {
   int frame_chunk_rows(int K, int interior_rows) const;
   void multi_step(int K, double* Tin, double* Tout, const double* iCp, int64_t nx, int64_t ny,
                   const Rect* rects, int n, const StencilTuning& tn, void* stream) const;
+  // ONE launch over the rect r alone (the whole pass of a rank without
+  // neighbours): pipelined kernels run graded task rows there (plan.h
+  // plan_row_bands: the rect as up to three row bands of descending rows per
+  // task) where the tile class has bands or RMA_DIAG task_rows forces them;
+  // anything else is multi_step over r as it is. RMA_DIAG task_rows=uniform
+  // and ExecParams::chunk_rows2 (uniform rows by request) switch grading off.
+  void launch_region(int K, double* Tin, double* Tout, const Rect& r, const StencilTuning& tn,
+                     void* stream);
+  std::vector<RowBand> region_bands(int K, const Rect& r, const StencilTuning& tn);
+  int rows_mode_ = 0;  // RMA_DIAG task_rows: 0 by tile class, 1 uniform, 2 rows_forced_
+  std::array<int, 3> rows_forced_{{0, 0, 0}};
+  double rows_fill_ = kBandFill;
+  struct BandSlots {  // resident blocks (CUs x blocks per CU) of the kernel asked last
+    int stages = 0, arith = 0, vec = 0, slots = 0;  // slots 0: not asked
+  };
+  std::vector<BandSlots> band_slots_;  // index K
+  int64_t graded_passes_ = 0;
   void exchange(double* A, stream_t s);
   bool cross_pass_ = false;  // this pass may use the one-group cross exchange (run_eager)
   void build_graph(int64_t steps, int reps);

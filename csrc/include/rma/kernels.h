@@ -70,6 +70,16 @@ struct StencilTuning {
   uint64_t* signal = nullptr;
   int signal_rects = 0;
   int signal_chunk_rows = 0;  // rows per task of the signal rects (0: chunk_rows)
+  // Graded task rows (pipelined kernels only): rect_rows[i] > 0 is the rows
+  // per task of rect i (nrects entries; else chunk_rows / signal_chunk_rows),
+  // and the last `bands` rects are row bands of one region with descending
+  // rows per task (plan.h plan_row_bands): dispatched in that order, each
+  // XCD-remapped among its own blocks, so every XCD walks long, then medium,
+  // then short tasks and the short ones fill the end of the launch. The band
+  // rects must be non-empty and follow the signal rects. Speed only: any task
+  // mapping computes the same cells.
+  const int* rect_rows = nullptr;
+  int bands = 0;
   // direct-store halos of this launch (pipelined kernels; nullptr: none)
   const DirectStores* direct = nullptr;
   // 1/Cp is bit-for-bit the one value uniform_value in every cell (the caller
@@ -156,6 +166,20 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
                             const double* iCp, int64_t nx, int64_t ny, const Rect* rects,
                             int nrects, const StencilCoef& c, const StencilTuning& tune,
                             stream_t stream);
+// The task of every block of a pipelined launch, computed on the host by the
+// function the kernel itself runs (stencil_device.h locate_strip_task over
+// plan_strip_tasks): out[3 b .. 3 b + 2] = (rect index among the non-empty
+// rects, strip, chunk) of block b; returns the block count (out == nullptr:
+// only counts). halo = K, V cells per lane, sw_block input columns per strip
+// task, rect_rows / bands as StencilTuning, sig_rects > 0: the blocks of the
+// first sig_rects rects are a signal prefix. For the CPU test of the mapping.
+int64_t pipe_task_map(const Rect* rects, int nrects, int V, int chunk_rows, int halo,
+                      int64_t sw_block, const int* rect_rows, int bands, int sig_rects, int remap,
+                      int64_t* out);
+// The grid the last stencil_pipe_rects_gpu call of this process launched:
+// out[0] = blocks, out[1] = the band count its kernel got (RectList::nbands).
+// Tests read it to see that a graded pass reached the device as planned.
+void pipe_last_launch(int64_t out[2]);
 // CPU twins of the fast5 arithmetic (one step / K steps, same operations and
 // rounding as kernels 5-9: std::fma, -ffp-contract=off); the intermediate
 // levels are updated on the interior only, like stencilk_rects_cpu.

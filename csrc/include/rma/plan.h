@@ -7,6 +7,7 @@
 
 #include <array>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "rma/common.h"
@@ -120,6 +121,45 @@ void apply_cost_overrides(std::vector<double>& cost, const char* spec);
 // --chunks): 4096^2 K=24 192 rows (-38 % vs r1's 32), 8192^2 256 (-23 %),
 // 16384^2 512 (-7 %); 0 = no table entry (the one-step kernels' rule).
 int pipe_chunk_rows(int K, int64_t ny, bool canonical);
+
+// Graded task rows of the deep pipelined passes. A task of c output rows runs
+// c + 2K + S - 2 row iterations, so long tasks waste the least work, but the
+// pass ends in a tail where block slots empty while the last tasks finish,
+// which grows with c; one chunk_rows for the whole tile trades one against
+// the other (profiles/r9/graded_rows.md). A graded launch runs very long tasks
+// over most of the rows, dispatched first, and short ones at the end to fill
+// the tail.
+//
+// plan_row_bands splits the rows [y0, y1) of a rect of `strips` strip columns
+// into at most three bands of rows[0] > rows[1] > rows[2] rows per task (a 0
+// entry drops that band), top to bottom = dispatch order. The two short bands
+// are sized to about fill * slots tasks each (slots: blocks resident on the
+// device, CUs x blocks per CU), at most a quarter of the range each; every
+// band but the last is a whole number of its own tasks and the remainder
+// moves down into the next band. A range too short for one task of rows[0]
+// beside the short bands, or rows without a second entry, returns the single
+// band {y0, y1, uniform_rows}: today's geometry.
+struct RowBand {
+  int64_t y0 = 0, y1 = 0;
+  int rows = 0;  // rows per task
+};
+constexpr double kBandFill = 2.0;  // short bands: tasks per resident block slot (measured)
+std::vector<RowBand> plan_row_bands(int64_t y0, int64_t y1, int64_t strips, int64_t slots,
+                                    const std::array<int, 3>& rows, int uniform_rows,
+                                    double fill = kBandFill);
+// Band rows per tile class and depth, measured (profiles/r9/graded_rows.md);
+// {0, 0, 0}: no grading on this class.
+std::array<int, 3> pipe_band_rows(int K, int64_t ny);
+// Strip columns of a pipelined launch over the columns [x0, x1) at depth K and
+// V cells per lane, one column wave (stencil_device.h plan_strip_tasks).
+int64_t pipe_strip_count(int64_t x0, int64_t x1, int K, int V);
+// RMA_DIAG task_rows: "" (by tile class), "uniform" (never graded) or
+// "r0/r1/r2[/fill]" (these bands on any tile: r0 >= 1, the non-zero entries
+// descending, at least one of r1 / r2). Returns false for "" and "uniform"
+// (uniform set accordingly); throws on anything else, so a bad value is
+// refused where the key is read, not at the first graded launch.
+bool parse_task_rows(const std::string& spec, std::array<int, 3>& rows, double& fill,
+                     bool& uniform);
 
 // Decompose n steps into passes of 1..Kmax steps minimising the summed cost
 // (dynamic programme; ties -> fewer passes). Returned deepest first. E.g. the

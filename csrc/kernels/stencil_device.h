@@ -36,6 +36,10 @@ struct RectList {
                                  // 0: linear task mapping, -1: column mode (thin rects)
   int64_t crows[kMaxRects];      // pipelined kernels: rows per task of each rect
   int n;
+  // graded task rows (pipelined kernels): the last nbands rects are row bands
+  // of one region with descending rows per task, in dispatch order; the XCD
+  // remap then stays inside each band (locate_strip_task). 0 / 1: no bands.
+  int nbands;
   // frame-first fused pass (pipelined kernels; executor RMA_EXEC_FUSED): the
   // first sig_blocks blocks (the frame rects' tasks, dispatched first, never
   // XCD-remapped) count their completion in sig[0]; the last one re-arms the
@@ -110,7 +114,7 @@ __device__ __forceinline__ void store_row(double* __restrict__ p, const double (
 // keeps both neighbours on the same XCD (same L2) whatever the strip count.
 // Bijective for any grid size (cdna_hip_programming.md "XCD swizzle must be
 // bijective"). Speed only: any mapping computes the same cells.
-__device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nwg) {
+__host__ __device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nwg) {
   constexpr int64_t kXcd = 8;
   if (nwg < kXcd) return b;
   const int64_t q = nwg / kXcd, r = nwg % kXcd;
@@ -120,8 +124,55 @@ __device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nwg) {
 
 // Block b of a launch whose first `first` blocks keep dispatch order (the
 // frame tasks of a fused pass) and whose rest is XCD-remapped among itself.
-__device__ __forceinline__ int64_t xcd_remap_after(int64_t b, int64_t nwg, int64_t first) {
+__host__ __device__ __forceinline__ int64_t xcd_remap_after(int64_t b, int64_t nwg,
+                                                            int64_t first) {
   return b < first ? b : first + xcd_remap(b - first, nwg - first);
+}
+
+// The (rect, strip, chunk) task of block blk of a pipelined launch of nwg
+// blocks planned by plan_strip_tasks (block b of a rect: chunk = lb / strips,
+// strip = lb % strips). remap: the blocks after the signal prefix
+// (RectList::sig_blocks, dispatch order kept) are XCD-remapped, all among
+// themselves without bands (xcd_remap_after) or, with nbands > 1, each band
+// among its own blocks and the rects before the bands among theirs: one
+// contiguous eighth of the WHOLE range per XCD would put every short task of
+// the last band on the last XCD, whereas every XCD should walk long, then
+// medium, then short tasks in dispatch order. Consecutive blocks go to
+// consecutive XCDs wherever a segment starts, so blocks s + j, s + j + 8, ...
+// of a segment [s, e) share an XCD and xcd_remap(b - s, e - s) hands each XCD a
+// contiguous piece of the segment. Bijective for any sizes; host-callable for
+// the CPU test of the mapping (pipe_task_map).
+struct StripTask {
+  int ri;
+  int64_t strip, chunk;
+};
+__host__ __device__ __forceinline__ StripTask locate_strip_task(const RectList& L, int64_t blk,
+                                                                int64_t nwg, int remap) {
+  const int64_t first = L.sig ? L.sig_blocks : 0;
+  int64_t b = blk;
+  if (remap && b >= first) {
+    int64_t s = first, e = nwg;
+    if (L.nbands > 1) {
+      const int fb = L.n - L.nbands;  // the first band rect (its blocks follow the prefix)
+      const int64_t bs = fb ? L.block_end[fb - 1] : 0;
+      if (b < bs) {
+        e = bs;
+      } else {
+        int i = fb;
+        while (i < L.n - 1 && b >= L.block_end[i]) ++i;
+        s = i ? L.block_end[i - 1] : 0;
+        e = L.block_end[i];
+      }
+    }
+    b = s + xcd_remap(b - s, e - s);
+  }
+  StripTask t;
+  t.ri = 0;
+  while (t.ri < L.n - 1 && b >= L.block_end[t.ri]) ++t.ri;
+  const int64_t lb = b - (t.ri ? L.block_end[t.ri - 1] : 0);
+  t.strip = lb % L.strips[t.ri];
+  t.chunk = lb / L.strips[t.ri];
+  return t;
 }
 
 // End of a signalling block (RectList::sig): every wave's stores are complete

@@ -292,12 +292,9 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   // waves c*S .. c*S+S-1: column c, one per SIMD (waves are dealt to SIMDs in order)
   const int stage = wv % S;
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t sig_first = L.sig ? L.sig_blocks : 0;
-  const int64_t b = remap ? xcd_remap_after(blockIdx.x, gridDim.x, sig_first) : (int64_t)blockIdx.x;
-  int ri = 0;
-  while (ri < L.n - 1 && b >= L.block_end[ri]) ++ri;
-  const int64_t lb = b - (ri ? L.block_end[ri - 1] : 0);
-  const int64_t strip = lb % L.strips[ri], chunk = lb / L.strips[ri];
+  const StripTask task = locate_strip_task(L, blockIdx.x, gridDim.x, remap);
+  const int ri = task.ri;
+  const int64_t strip = task.strip, chunk = task.chunk;
   const Rect r = L.r[ri];
   const int64_t xs = L.xa[ri] + strip * kStep;
   const int64_t crows = L.crows[ri];  // == chunk_rows unless a fused pass's frame rect
@@ -803,7 +800,8 @@ __device__ __forceinline__ void pipe_body(double* __restrict__ T2, const double*
   if constexpr (kGlds) {
     if (stage == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  if (b < sig_first) signal_block_done(L.sig, L.sig_blocks);  // block-uniform
+  // the signal prefix keeps dispatch order (locate_strip_task); block-uniform
+  if (L.sig && (int64_t)blockIdx.x < L.sig_blocks) signal_block_done(L.sig, L.sig_blocks);
 }
 
 // Dir: the direct-store halo variant (DirectStores). A separate instantiation:
@@ -856,6 +854,11 @@ struct PipeLaunch {
                              // plain kernel [0] and of its direct-store variant [1] (0: none)
   int uniform = 0;  // 1/Cp is the one value c0: run the uniform-factor variant where the
   double c0 = 0.0;  // instantiation has one and the launch stores no halos directly
+  // graded task rows (StencilTuning::rect_rows / bands): rows per task of each
+  // rect where > 0, and the trailing rects that are row bands (RectList::nbands)
+  const int* rect_rows = nullptr;
+  int bands = 0;
+  int64_t* planned = nullptr;  // non-null: receives {blocks, RectList::nbands} of the launch
 };
 
 // Plans the (strip, chunk) tasks with this instantiation's block width
@@ -883,12 +886,22 @@ void launch(const PipeLaunch& a) {
     for (int i = 0; i < a.sig_rects && i < kMaxRects; ++i) rows_buf[i] = a.sig_chunk_rows;
     rows = rows_buf;
   }
+  if (a.rect_rows) {
+    for (int i = 0; i < a.nrects && i < kMaxRects; ++i)
+      if (a.rect_rows[i] > 0) rows_buf[i] = a.rect_rows[i];
+    rows = rows_buf;
+  }
   RectList L;
   const int64_t blocks =
       plan_strip_tasks(L, a.rects, a.nrects, V, a.chunk_rows, K, Geo<K, S, V, C>::WB, rows);
   static_assert(Geo<K, S, V, C>::kStep == (Geo<K, S, V, C>::WB - 2 * K) / V * V, "strip step");
   if (L.n == 0) return;
   RMA_CHECK_ARG(blocks < (int64_t(1) << 31), "grid too large: " << blocks << " blocks");
+  L.nbands = a.bands;  // (the launcher checked: non-empty rects after the signal rects)
+  if (a.planned) {
+    a.planned[0] = blocks;
+    a.planned[1] = L.nbands;
+  }
   if (a.sig) {  // the signal rects' blocks (empty rects are not planned)
     int ns = 0;
     for (int i = 0; i < a.sig_rects; ++i) ns += a.rects[i].empty() ? 0 : 1;

@@ -5,6 +5,7 @@
 // pipe_has_cols admit goes to the lab library (lab_hooks.h).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 
 #include "rma/hip_check.h"
@@ -31,6 +32,51 @@ void stencil_pipe_occupancy(int K, int stages, int arith, int V, int occ[2]) {
            pipe::dispatch_r(K, S, V, arith, a) ||
            pipe::dispatch_a(K, S, V, arith, a) ||
            pipe::dispatch_b(K, S, V, arith, a) || pipe::dispatch_c(K, S, V, arith, a));
+}
+
+namespace {
+// what the last pipelined launch of this process handed to its kernel
+std::atomic<int64_t> g_last_blocks{0}, g_last_bands{0};
+}  // namespace
+
+void pipe_last_launch(int64_t out[2]) {
+  out[0] = g_last_blocks.load();
+  out[1] = g_last_bands.load();
+}
+
+int64_t pipe_task_map(const Rect* rects, int nrects, int V, int chunk_rows, int halo,
+                      int64_t sw_block, const int* rect_rows, int bands, int sig_rects, int remap,
+                      int64_t* out) {
+  RMA_CHECK_ARG(nrects >= 0 && nrects <= kMaxRects, "nrects=" << nrects);
+  RMA_CHECK_ARG(V >= 1 && chunk_rows >= 1 && halo >= 0, "V=" << V << " chunk_rows=" << chunk_rows
+                                                             << " halo=" << halo);
+  RMA_CHECK_ARG((sw_block > 0 ? sw_block : 64 * V) - 2 * halo >= V, "strip narrower than its halo");
+  RMA_CHECK_ARG(sig_rects >= 0 && bands >= 0 && bands <= nrects - sig_rects,
+                "bands=" << bands << " sig_rects=" << sig_rects << " of " << nrects << " rects");
+  int ns = 0;
+  for (int i = 0; i < nrects; ++i) {
+    RMA_CHECK_ARG(!rect_rows || rect_rows[i] >= 0, "rect_rows[" << i << "]");
+    RMA_CHECK_ARG(i < nrects - bands || !rects[i].empty(), "band rect " << i << " is empty");
+    if (i < sig_rects && !rects[i].empty()) ++ns;
+  }
+  march::RectList L;
+  const int64_t blocks =
+      march::plan_strip_tasks(L, rects, nrects, V, chunk_rows, halo, sw_block, rect_rows);
+  if (L.n == 0) return 0;
+  L.nbands = bands;
+  static uint64_t dummy[2];  // a signalling launch is one with RectList::sig set (never read here)
+  if (ns > 0) {
+    L.sig = dummy;
+    L.sig_blocks = L.block_end[ns - 1];
+  }
+  if (out)
+    for (int64_t b = 0; b < blocks; ++b) {
+      const march::StripTask t = march::locate_strip_task(L, b, blocks, remap);
+      out[3 * b] = t.ri;
+      out[3 * b + 1] = t.strip;
+      out[3 * b + 2] = t.chunk;
+    }
+  return blocks;
 }
 
 void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const double* T,
@@ -104,6 +150,20 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
     RMA_CHECK_ARG(tune.signal_chunk_rows >= 0, "signal_chunk_rows=" << tune.signal_chunk_rows);
     a.sig_chunk_rows = tune.signal_chunk_rows;
   }
+  if (tune.rect_rows)
+    for (int i = 0; i < nrects; ++i)
+      RMA_CHECK_ARG(tune.rect_rows[i] >= 0, "rect_rows[" << i << "]=" << tune.rect_rows[i]);
+  a.rect_rows = tune.rect_rows;
+  if (tune.bands > 0) {  // the trailing rects are row bands (RectList::nbands)
+    RMA_CHECK_ARG(tune.bands <= nrects - a.sig_rects,
+                  "bands=" << tune.bands << " of " << nrects << " rects, " << a.sig_rects
+                           << " of them signal rects");
+    for (int i = nrects - tune.bands; i < nrects; ++i)
+      RMA_CHECK_ARG(!rects[i].empty(), "band rect " << i << " is empty");
+    a.bands = tune.bands;
+  }
+  int64_t planned[2] = {0, 0};
+  a.planned = planned;
   // V = 5 only in the lab (the core units' cases take any V other than 4 and 2 as 1)
   bool ok = C == 1 && V != 5 &&
             (pipe::dispatch_r20(K, S, V, arith, a) || pipe::dispatch_r24(K, S, V, arith, a) ||
@@ -118,6 +178,8 @@ void stencil_pipe_rects_gpu(int K, int stages, int arith, double* T2, const doub
   RMA_CHECK_ARG(ok, "pipelined kernel K=" << K << " S=" << S << " V=" << V << " C=" << C
                                            << " arithmetic=" << arith << " not instantiated");
   RMA_HIP_LAUNCH_CHECK();
+  g_last_blocks.store(planned[0]);
+  g_last_bands.store(planned[1]);
 }
 
 }  // namespace rma

@@ -218,6 +218,12 @@ DiffusionExecutor::DiffusionExecutor(double* T, double* T2, const double* iCp, i
   fused_ = fu == "auto" ? 2 : fu == "1" ? 1 : 0;
   // bounded wait of the exchange stream for the frame tasks' flag (seconds)
   fused_timeout_s_ = env_double("RMA_EXEC_FUSED_TIMEOUT", 60.0, 1e-9, 1e6);
+  {  // RMA_DIAG task_rows=uniform | r0/r1/r2[/fill] (launch_region)
+    bool uni = false;
+    const bool forced = parse_task_rows(diag_value("task_rows"), rows_forced_, rows_fill_, uni);
+    rows_mode_ = forced ? 2 : uni ? 1 : 0;
+    band_slots_.assign(kPipeMaxK + 1, BandSlots{});
+  }
   {
     int dev = 0, cus = 0;
     RMA_HIP_CHECK(hipGetDevice(&dev));
@@ -541,6 +547,58 @@ void DiffusionExecutor::multi_step(int K, double* Tin, double* Tout, const doubl
   stencilk_rects_gpu(K, Tout, Tin, iCp, nx, ny, rects, n, p_.coef, tu, stream);
 }
 
+std::vector<RowBand> DiffusionExecutor::region_bands(int K, const Rect& r,
+                                                     const StencilTuning& tn) {
+  const std::vector<RowBand> single{{r.y0, r.y1, tn.chunk_rows}};
+  bool alone = true;
+  // (real_nbr_: the solo passes of a rank with neighbours keep its uniform rows)
+  for (int d = 0; d < 2; ++d) alone = alone && real_nbr_[d][0] < 0 && real_nbr_[d][1] < 0;
+  const std::array<int, 3> rows = rows_mode_ == 2 ? rows_forced_ : pipe_band_rows(K, ny_);
+  if (tn.kernel < 9 || !alone || r.empty() || tn.direct || tn.signal || tn.signal_rects > 0 ||
+      rows_mode_ == 1 || (rows_mode_ == 0 && p_.chunk_rows2 > 0) || rows[0] <= 0)
+    return single;
+  // the cells per lane and stages the launcher resolves (as geometry()); they
+  // size the bands only: any bands compute the same cells
+  const int arith = tn.kernel - 9;
+  const int S = tn.stages > 0 ? tn.stages : pipe_default_stages(K);
+  const int V = pipe_vec_uniform(K, tn.stages, arith, nx_, tn.vec, true, uniform_);
+  if (V < 1 || 64 * V - 2 * K < V) return single;
+  // resident blocks of this kernel (K, stages, arithmetic, cells per lane), asked once
+  BandSlots& bs = band_slots_[K];
+  if (bs.slots == 0 || bs.stages != S || bs.arith != arith || bs.vec != V) {
+    int occ[2] = {0, 0};
+    stencil_pipe_occupancy(K, S, arith, V, occ);
+    bs = {S, arith, V, cus_ * std::max(1, occ[0])};
+  }
+  return plan_row_bands(r.y0, r.y1, pipe_strip_count(r.x0, r.x1, K, V), bs.slots, rows,
+                        tn.chunk_rows, rows_fill_);
+}
+
+std::vector<RowBand> DiffusionExecutor::row_bands(int K, const Rect& r) {
+  return region_bands(K, r, pass_tuning(K, 0));
+}
+
+void DiffusionExecutor::launch_region(int K, double* Tin, double* Tout, const Rect& r,
+                                      const StencilTuning& tn, void* stream) {
+  const std::vector<RowBand> bands = region_bands(K, r, tn);
+  if (bands.size() < 2 || bands.size() > (size_t)kMaxRects) {
+    multi_step(K, Tin, Tout, iCp_, nx_, ny_, &r, 1, tn, stream);
+    return;
+  }
+  Rect rs[kMaxRects];
+  int rows[kMaxRects] = {};
+  int n = 0;
+  for (const RowBand& b : bands) {
+    rs[n] = {r.x0, r.x1, b.y0, b.y1};
+    rows[n++] = b.rows;
+  }
+  StencilTuning t = tn;
+  t.rect_rows = rows;
+  t.bands = n;
+  multi_step(K, Tin, Tout, iCp_, nx_, ny_, rs, n, t, stream);
+  ++graded_passes_;
+}
+
 bool DiffusionExecutor::fused_pass_ok(const PassGeom& g, const StencilTuning& tn) const {
   if (!sig_ || !g.aligned || tn.kernel < 9 || g.interior.empty()) return false;
   int nf = 0;
@@ -845,7 +903,7 @@ void DiffusionExecutor::enqueue_pass(int K, double* Tin, double* Tout) {
     rec(0, s_lo_);
     rec(3, s_lo_);
     dwait(s_lo_);
-    multi_step(K, Tin, Tout, iCp_, nx_, ny_, &g.out, 1, with_direct(tn), s_lo_);
+    launch_region(K, Tin, Tout, g.out, with_direct(tn), s_lo_);  // (graded without neighbours)
     rec(4, s_lo_);
     rec(1, s_lo_);
     if (da)
@@ -903,7 +961,8 @@ void DiffusionExecutor::enqueue_pass(int K, double* Tin, double* Tout) {
     RMA_HIP_CHECK(hipStreamWaitEvent(S(s_lo_), E(e_hi_), 0));
     rec(0, s_lo_);
     rec(3, s_lo_);
-    multi_step(K, Tin, Tout, iCp_, nx_, ny_, &g.interior, 1, tn, s_lo_);
+    // (graded task rows where the tile class has bands: launch_region)
+    launch_region(K, Tin, Tout, g.interior, tn, s_lo_);
     rec(4, s_lo_);
     rec(1, s_lo_);
     exchange(Tout, s_lo_);  // no-op without neighbours

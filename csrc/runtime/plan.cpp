@@ -262,6 +262,86 @@ int pipe_chunk_rows(int K, int64_t ny, bool canonical) {
   return 0;  // 32768^2 .. 101376^2: the r1 table is within 1-2 % of the best
 }
 
+std::vector<RowBand> plan_row_bands(int64_t y0, int64_t y1, int64_t strips, int64_t slots,
+                                    const std::array<int, 3>& rows, int uniform_rows,
+                                    double fill) {
+  RMA_CHECK_ARG(y1 > y0 && strips >= 1 && slots >= 1 && uniform_rows >= 1,
+                "row bands of [" << y0 << ", " << y1 << "), " << strips << " strips, " << slots
+                                 << " slots, " << uniform_rows << " rows per task");
+  RMA_CHECK_ARG(fill > 0.0 && fill <= 64.0, "band fill " << fill);
+  const std::vector<RowBand> single{{y0, y1, uniform_rows}};
+  if (rows[0] <= 0 || (rows[1] <= 0 && rows[2] <= 0)) return single;
+  int prev = rows[0];
+  for (int i = 1; i < 3; ++i) {
+    RMA_CHECK_ARG(rows[i] >= 0 && (rows[i] == 0 || rows[i] < prev),
+                  "band rows " << rows[0] << "/" << rows[1] << "/" << rows[2]
+                               << " must descend");
+    if (rows[i] > 0) prev = rows[i];
+  }
+  const int64_t R = y1 - y0;
+  // rows of a short band: about fill * slots tasks, at most a quarter of the range
+  const int64_t chunks = std::max<int64_t>(1, (int64_t)std::ceil(fill * (double)slots / (double)strips));
+  auto tail = [&](int r) { return r > 0 ? std::min(chunks * r, R / 4) : (int64_t)0; };
+  const int64_t t1 = tail(rows[1]), t2 = tail(rows[2]);
+  const int64_t n0 = (R - t1 - t2) / rows[0] * rows[0];
+  if (n0 <= 0) return single;
+  const int64_t rest = R - n0;
+  // without a third band the second takes the remainder
+  const int64_t n1 = rows[1] <= 0 ? 0 : rows[2] <= 0 ? rest : (rest - t2) / rows[1] * rows[1];
+  const int64_t n2 = rest - n1;
+  std::vector<RowBand> b{{y0, y0 + n0, rows[0]}};
+  if (n1 > 0) b.push_back({y0 + n0, y0 + n0 + n1, rows[1]});
+  if (n2 > 0) b.push_back({y0 + n0 + n1, y1, rows[2]});
+  return b;
+}
+
+std::array<int, 3> pipe_band_rows(int K, int64_t ny) {
+  // the 288 GB tile class, K = 20..24: six-cell uniform passes at 101120^2,
+  // interleaved with 3072 uniform rows, K = 24 60.66 vs 61.87 ms (-2.0 %), K = 20
+  // 55.33 vs 56.06 ms (-1.3 %); 6144/1536/384, 12288/3072/768 and 3072/768/192
+  // are within 0.5 % of it (profiles/r9/graded_rows.md section 2). Smaller
+  // classes and depths were not measured and stay uniform
+  if (K >= 20 && ny >= 98304) return {6144, 768, 192};
+  return {0, 0, 0};
+}
+
+int64_t pipe_strip_count(int64_t x0, int64_t x1, int K, int V) {
+  RMA_CHECK_ARG(V >= 1 && K >= 1 && 64 * V - 2 * K >= V && x1 > x0,
+                "strips of [" << x0 << ", " << x1 << ") at K=" << K << " V=" << V);
+  const int64_t step = (64 * V - 2 * K) / V * V;
+  const int64_t xs = x0 - K, xa = xs - (((xs % V) + V) % V);
+  return (x1 - (xa + K) + step - 1) / step;
+}
+
+bool parse_task_rows(const std::string& spec, std::array<int, 3>& rows, double& fill,
+                     bool& uniform) {
+  uniform = spec == "uniform";
+  if (spec.empty() || uniform) return false;
+  double v[4] = {0, 0, 0, kBandFill};
+  int n = 0;
+  size_t pos = 0;
+  bool ok = true;
+  while (ok && pos <= spec.size()) {
+    const size_t end = std::min(spec.find('/', pos), spec.size());
+    const std::string item = spec.substr(pos, end - pos);
+    char* e = nullptr;
+    const double x = std::strtod(item.c_str(), &e);
+    ok = n < 4 && !item.empty() && e && *e == '\0' && std::isfinite(x) && x >= 0 && x < (1 << 30);
+    if (ok) v[n++] = x;
+    pos = end + 1;
+  }
+  ok = ok && n >= 3 && v[0] >= 1 && v[0] == std::floor(v[0]) && v[1] == std::floor(v[1]) &&
+       v[2] == std::floor(v[2]) && v[3] > 0 && v[3] <= 64;
+  // the non-zero rows descend and there is a second band (as plan_row_bands asks)
+  ok = ok && (v[1] > 0 || v[2] > 0) && (v[1] == 0 || v[1] < v[0]) &&
+       (v[2] == 0 || v[2] < (v[1] > 0 ? v[1] : v[0]));
+  RMA_CHECK_ARG(ok, "RMA_DIAG task_rows=" << spec
+                        << " (uniform | r0/r1/r2[/fill], rows per task descending)");
+  rows = {(int)v[0], (int)v[1], (int)v[2]};
+  fill = v[3];
+  return true;
+}
+
 std::vector<double> default_pass_costs(int kmax, bool fast5, double cells) {
   RMA_CHECK_ARG(kmax >= 1 && kmax <= 24, "kmax=" << kmax << " (tables cover 1..24)");
   // the measured tile class nearest in log(cells); 0 = the 288 GB tile

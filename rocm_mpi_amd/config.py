@@ -39,6 +39,7 @@ DIAG_KEYS = {
     "pass_costs": "K:cost/K:cost/...: planner cost overrides",
     "uniform_factor": "off: the 1/Cp field path also where 1/Cp is one value",
     "pipe_cells": "4 | 6: uniform passes at four cells everywhere / six on every tile",
+    "task_rows": "uniform | r0/r1/r2[/fill]: graded task rows off / forced on any tile",
     # communication (C++)
     "rccl_data_blocking": "blocking RCCL data path of a non-blocking communicator",
     "rccl_graph": "allow hipGraph capture over RCCL",
