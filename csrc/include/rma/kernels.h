@@ -260,6 +260,20 @@ struct Dispatch3D {
 void plan_dispatch3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning& tune,
                      Dispatch3D* out);
 const char* path3d_name(int path);  // "none", "march", "thin", "xface"
+// The boxes of a launch sorted by plan_dispatch3d's path (kernel_select.cpp, host
+// only; both launchers run it): wide[0..nwide) the boxes of the march launch,
+// thin[i] marking those on the thin-box path, and face[c][0..nface[c]) the boxes
+// of the x-face launch of lanes-per-row class c (8, 16, 32 lanes). Empty boxes
+// are in no list; every list keeps the caller's order, which fixes the launch order.
+struct Split3D {
+  Box wide[kMaxBoxes];
+  bool thin[kMaxBoxes] = {};
+  int nwide = 0;
+  Box face[3][kMaxBoxes];
+  int nface[3] = {0, 0, 0};
+  bool faces() const { return nface[0] + nface[1] + nface[2] > 0; }
+};
+Split3D split_boxes3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning& tune);
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
 // Cells per lane both 3D launchers run: tune.vec with even nx and 16-byte

@@ -1,7 +1,8 @@
 // Host-side kernel-selection rules of the stencil launchers: which
 // pipelined (K, stages, arithmetic, cols) instantiations exist, the cells per
 // lane a launch runs, the one-step march kernel's strip width, the path of every
-// box of a 3D launch (plan_dispatch3d). Plain host code
+// box of a 3D launch (plan_dispatch3d) and the box lists both 3D launchers
+// build from it (split_boxes3d). Plain host code
 // (moved out of stencil_pipe.hip / stencil.hip) so the executor's planning
 // compiles and runs without HIP, e.g. in tests/native/executor_selftest.cpp
 // under ThreadSanitizer / AddressSanitizer.
@@ -111,6 +112,22 @@ void plan_dispatch3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning&
       out[i].lanes = 64;
     }
   }
+}
+
+Split3D split_boxes3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning& tune) {
+  Dispatch3D path[kMaxBoxes];
+  plan_dispatch3d(K, boxes, nboxes, tune, path);
+  Split3D s;
+  for (int i = 0; i < nboxes; ++i) {
+    if (path[i].path == kPathXface) {
+      const int cls = path[i].lanes == 8 ? 0 : path[i].lanes == 16 ? 1 : 2;
+      s.face[cls][s.nface[cls]++] = boxes[i];
+    } else if (path[i].path != kPathNone) {
+      s.thin[s.nwide] = path[i].path == kPathThin;
+      s.wide[s.nwide++] = boxes[i];
+    }
+  }
+  return s;
 }
 
 const char* path3d_name(int path) {

@@ -49,46 +49,11 @@
 
 #include "rma/hip_check.h"
 #include "rma/kernels.h"
-#include "stencil_device.h"
+#include "stencil3d_device.h"
 
 namespace rma {
 namespace {
 using namespace march;
-
-struct BoxList {
-  Box b[kMaxBoxes];
-  int64_t xa[kMaxBoxes];         // strip origin (x0 rounded down to the strip width)
-  int64_t strips[kMaxBoxes];
-  int64_t bands[kMaxBoxes];
-  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / waves per block)
-  int64_t chunk_z[kMaxBoxes];    // planes per task; -1: thin box, one thread per row
-  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
-  int n;
-};
-
-__device__ __forceinline__ double cell3(double xl, double c, double xr, double up, double dn,
-                                        double bk, double fr, double ic, const StencilCoef3& k) {
-  const double qxR = (k.mlam * (xr - c)) * k.rdx;
-  const double qxL = (k.mlam * (c - xl)) * k.rdx;
-  const double qyU = (k.mlam * (dn - c)) * k.rdy;
-  const double qyD = (k.mlam * (c - up)) * k.rdy;
-  const double qzF = (k.mlam * (fr - c)) * k.rdz;
-  const double qzB = (k.mlam * (c - bk)) * k.rdz;
-  return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
-}
-
-// the update of one cell in arithmetic A (f: 1/Cp of the cell, or what Factor<true> holds)
-template <int A, bool Uni>
-__device__ __forceinline__ double update3(double xl, double c, double xr, double up, double dn,
-                                          double bk, double fr, double f, const Coef3<A>& k) {
-  if constexpr (A == kFast7) return cell7<Uni>(xl, c, xr, up, dn, bk, fr, f, k);
-  else return cell3(xl, c, xr, up, dn, bk, fr, f, k);
-}
-
-// 1/Cp as the kernels take it: the array, or with Uni its one value (fast7: gs
-// times that value)
-template <bool Uni>
-using Factor = std::conditional_t<Uni, double, const double* __restrict__>;
 
 // Addresses and masks of one wave task, constant along the march.
 template <int V, int R>
@@ -175,11 +140,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
                                                                  int64_t nx, int64_t ny,
                                                                  BoxList L, Coef3<A> k,
                                                                  int remap) {
-  const int64_t b = remap ? xcd_remap(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int bi = 0;
-  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
-  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const auto [bi, lb, wave] = locate_block(L, remap);
   const Box box = L.b[bi];
   const int64_t plane = nx * ny;
   if (L.chunk_z[bi] < 0) {
@@ -195,6 +156,8 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
       if constexpr (Uni) f = iCp; else f = iCp[o + x];
       const double v = update3<A, Uni>(T[o + x - 1], T[o + x], T[o + x + 1], T[o - nx + x],
                                        T[o + nx + x], T[o - plane + x], T[o + plane + x], f, k);
+      // written out, not store1: through the helper the 20 plain-store uniform
+      // instantiations compile to other registers and SGPR spills than they had
       if constexpr (NTS) {
         __builtin_nontemporal_store(v, T2 + o + x);
       } else {
@@ -241,38 +204,6 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
   }
 }
 
-// thin[i]: boxes[i] runs the thin-box path (plan_dispatch3d's kPathThin)
-int64_t plan_boxes(BoxList& L, const Box* boxes, const bool* thin, int nboxes, int V, int R,
-                   int chunk_z) {
-  L = BoxList{};
-  int64_t total = 0;
-  const int64_t sw = (int64_t)kWave * V;
-  for (int i = 0; i < nboxes; ++i) {
-    const Box& b = boxes[i];
-    if (b.empty()) continue;
-    const int n = L.n++;
-    L.b[n] = b;
-    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
-    int64_t blocks;
-    if (thin[i]) {
-      L.chunk_z[n] = -1;
-      blocks = (nyb * nzb + kBlock - 1) / kBlock;
-    } else {
-      L.xa[n] = b.x0 - (b.x0 % sw);
-      L.strips[n] = (b.x1 - L.xa[n] + sw - 1) / sw;
-      L.bands[n] = (nyb + R - 1) / R;
-      L.groups[n] = (L.bands[n] + kWavesPerBlock - 1) / kWavesPerBlock;
-      // 32 planes per task (measured, profiles/diffusion3d.md: 3-8 % ahead of 128
-      // at 1024^3 and 1536^3, level at 512^3); each chunk re-reads two planes
-      L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : 32, nzb);
-      blocks = L.strips[n] * L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
-    }
-    total += blocks;
-    L.block_end[n] = total;
-  }
-  return total;
-}
-
 // ---------------------------------------------------------------------------
 // x-face path (Stencil3DTuning::xface): boxes at most 32 cells wide in x, the
 // x slabs of a frame / interior split. The strip march would load 128 cells a
@@ -297,15 +228,6 @@ int64_t plan_boxes(BoxList& L, const Box* boxes, const bool* thin, int nboxes, i
 // before this path was added (the launcher splits the box list on the host; the
 // march kernel is untouched).
 // ---------------------------------------------------------------------------
-struct FaceList {
-  Box b[kMaxBoxes];
-  int64_t bands[kMaxBoxes];      // wave tasks along y: ceil(rows / (64 / LX))
-  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / waves per block)
-  int64_t chunk_z[kMaxBoxes];    // planes per task
-  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
-  int n;
-};
-
 template <int LX, bool NTS, bool Uni, int A>
 __global__ __launch_bounds__(kBlock) void stencil3d_xface_kernel(double* __restrict__ T2,
                                                                  const double* __restrict__ T,
@@ -314,11 +236,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_xface_kernel(double* __restr
                                                                  Coef3<A> k) {
   constexpr int RG = kWave / LX;  // rows of a wave
   static_assert(LX == 8 || LX == 16 || LX == 32, "lanes per row");
-  const int64_t b = blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int bi = 0;
-  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
-  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const auto [bi, lb, wave] = locate_block(L, 0);
   const Box box = L.b[bi];
   // block lb of a box: the group of 4 bands fastest, then the z chunk
   const int64_t band = (lb % L.groups[bi]) * kWavesPerBlock + wave;
@@ -357,13 +275,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_xface_kernel(double* __restr
     if (r == 0) up = h;
     if (r == RG - 1) dn = h;
     const double v = update3<A, Uni>(left, c, right, up, dn, bk, fr, f, k);
-    if (m) {
-      if constexpr (NTS) {
-        __builtin_nontemporal_store(v, T2 + z * plane + o);
-      } else {
-        T2[z * plane + o] = v;
-      }
-    }
+    if (m) store1<NTS>(T2 + z * plane + o, v);
     bk = c;
     c = fr;
     fr = fr2;
@@ -373,108 +285,16 @@ __global__ __launch_bounds__(kBlock) void stencil3d_xface_kernel(double* __restr
   }
 }
 
-// index of a lanes-per-row class (Dispatch3D::lanes): 0, 1, 2 for LX = 8, 16, 32
-int face_class(int lanes) { return lanes == 8 ? 0 : lanes == 16 ? 1 : 2; }
-
-int64_t plan_faces(FaceList& L, const Box* boxes, int nboxes, int LX, int chunk_z) {
-  L = FaceList{};
-  int64_t total = 0;
-  const int64_t rg = kWave / LX;
-  for (int i = 0; i < nboxes; ++i) {
-    const Box& b = boxes[i];
-    const int n = L.n++;
-    L.b[n] = b;
-    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
-    L.bands[n] = (nyb + rg - 1) / rg;
-    L.groups[n] = (L.bands[n] + kWavesPerBlock - 1) / kWavesPerBlock;
-    // 16 planes per task by default: a face has few cells, shorter tasks keep
-    // more waves in flight for the 2/16 re-read of the planes around a chunk
-    L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : 16, nzb);
-    total += L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
-    L.block_end[n] = total;
-  }
-  return total;
+// f(R, U) for the instantiated (rows, unroll) pairs: the list stencil3d_has accepts
+template <class F>
+void with_rows_unroll(int R, int U, F&& f) {
+  if (R == 2 && U == 1) f(int_c<2>{}, int_c<1>{});
+  else if (R == 2 && U == 2) f(int_c<2>{}, int_c<2>{});
+  else if (R == 4 && U == 1) f(int_c<4>{}, int_c<1>{});
+  else if (R == 4 && U == 2) f(int_c<4>{}, int_c<2>{});
+  else if (R == 8 && U == 1) f(int_c<8>{}, int_c<1>{});
+  else RMA_CHECK_ARG(false, "rows=" << R << " unroll=" << U << " has no instantiation");
 }
-
-template <int LX, int A>
-void launch_face(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-                 int64_t nx, int64_t ny, const FaceList& L, const Coef3<A>& c, bool uni,
-                 double fac) {
-  const dim3 block(kBlock);
-  if (uni) {
-    if (nt & 1)
-      stencil3d_xface_kernel<LX, true, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny, L, c);
-    else
-      stencil3d_xface_kernel<LX, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny, L, c);
-  } else if (nt & 1) {
-    stencil3d_xface_kernel<LX, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L, c);
-  } else {
-    stencil3d_xface_kernel<LX, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L, c);
-  }
-}
-
-// the face boxes of one launch, one kernel launch per lanes-per-row class in use
-template <int A>
-void launch_faces(const Box (&face)[3][kMaxBoxes], const int (&nface)[3], int chunk_z,
-                  hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-                  int64_t nx, int64_t ny, const Coef3<A>& c, bool uni, double fac) {
-  for (int cls = 0; cls < 3; ++cls) {
-    if (!nface[cls]) continue;
-    FaceList L{};
-    const int64_t total = plan_faces(L, face[cls], nface[cls], 8 << cls, chunk_z);
-    RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
-    const dim3 grid((unsigned)total);
-    if (cls == 0) launch_face<8, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, uni, fac);
-    else if (cls == 1) launch_face<16, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, uni, fac);
-    else launch_face<32, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, uni, fac);
-    RMA_HIP_LAUNCH_CHECK();
-  }
-}
-
-template <int V, int R, int U, int A>
-void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-               int64_t nx, int64_t ny, const BoxList& L, const Coef3<A>& c, int remap,
-               bool uni, double fac) {
-  const dim3 block(kBlock);
-  if (uni) {  // the 1/Cp-load bit has nothing to act on
-    if (nt & 1)
-      stencil3d_march_kernel<V, R, U, true, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
-                                                                                L, c, remap);
-    else
-      stencil3d_march_kernel<V, R, U, false, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx,
-                                                                                 ny, L, c, remap);
-    return;
-  }
-  switch (nt & 3) {
-    case 0:
-      stencil3d_march_kernel<V, R, U, false, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
-                                                                           c, remap);
-      break;
-    case 1:
-      stencil3d_march_kernel<V, R, U, true, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
-                                                                          c, remap);
-      break;
-    case 2:
-      stencil3d_march_kernel<V, R, U, false, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
-                                                                          c, remap);
-      break;
-    default:
-      stencil3d_march_kernel<V, R, U, true, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, L,
-                                                                         c, remap);
-  }
-}
-
-template <int V, int A>
-void launch_ru(int R, int U, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
-               const double* iCp, int64_t nx, int64_t ny, const BoxList& L,
-               const Coef3<A>& c, int remap, bool uni, double fac) {
-  if (R == 2 && U == 1) launch_nt<V, 2, 1, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else if (R == 2) launch_nt<V, 2, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else if (R == 4 && U == 1) launch_nt<V, 4, 1, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else if (R == 4) launch_nt<V, 4, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-  else launch_nt<V, 8, 1, A>(grid, s, nt, T2, T, iCp, nx, ny, L, c, remap, uni, fac);
-}
-
 }  // namespace
 
 bool stencil3d_has(int rows, int unroll) {
@@ -496,65 +316,50 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
   RMA_CHECK_ARG(stencil3d_has(tune.rows, tune.unroll),
                 "rows=" << tune.rows << " unroll=" << tune.unroll
                         << ": rows 2 or 4 with unroll 1 or 2, or rows 8 with unroll 1");
-  RMA_CHECK_ARG(tune.vec == 1 || tune.vec == 2, "vec=" << tune.vec << " (1 or 2)");
-  RMA_CHECK_ARG(tune.nontemporal >= 0 && tune.nontemporal <= 3,
-                "nontemporal=" << tune.nontemporal << " (bits 0 and 1)");
-  RMA_CHECK_ARG(tune.chunk_z >= 0, "chunk_z=" << tune.chunk_z);
-  RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
-                "fast_math: fast7 needs lam != 0 and finite coefficients");
-  // plan_dispatch3d (kernel_select.cpp) checks tune.xface and decides the path of
-  // every box: face boxes leave the list for the x-face kernel, the rest keep
-  // their order in the march launch (strips, or one thread per row for thin
-  // boxes). xface = 0 has no face boxes: the caller's list.
-  Dispatch3D path[kMaxBoxes];
-  plan_dispatch3d(1, boxes, nboxes, tune, path);
-  hipStream_t s = as_stream(stream);
-  Box wide[kMaxBoxes], face[3][kMaxBoxes];
-  bool thin[kMaxBoxes];
-  int nwide = 0, nface[3] = {0, 0, 0};
-  for (int i = 0; i < nboxes; ++i) {
-    if (path[i].path == kPathXface) {
-      const int cls = face_class(path[i].lanes);
-      face[cls][nface[cls]++] = boxes[i];
-    } else if (path[i].path != kPathNone) {
-      thin[nwide] = path[i].path == kPathThin;
-      wide[nwide++] = boxes[i];
-    }
-  }
-  const bool faces = nface[0] + nface[1] + nface[2] > 0;
+  check_tuning3d(tune, c, "", tune.nontemporal, tune.chunk_z);
+  // split_boxes3d (kernel_select.cpp) checks tune.xface and sorts the boxes by
+  // plan_dispatch3d's path: face boxes leave the list for the x-face kernel, the
+  // rest keep their order in the march launch (strips, or one thread per row for
+  // thin boxes). xface = 0 has no face boxes: the caller's list.
+  const Split3D sp = split_boxes3d(1, boxes, nboxes, tune);
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
-  const int64_t total = plan_boxes(L, wide, thin, nwide, V, tune.rows, tune.chunk_z);
-  if (L.n == 0 && !faces) return;
-  RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
-  const dim3 grid((unsigned)total);
-  const int remap = tune.xcd_remap ? 1 : 0;
-  if (tune.fast_math) {  // the uniform variant takes g = gs * value, formed here
-    const Fast7 f = fast7_constants(c);
-    const double g = f.gs * tune.uniform_value;
-    if (faces)
-      launch_faces<kFast7>(face, nface, tune.chunk_z, s, tune.nontemporal, T2, T, iCp, nx, ny, f,
-                           tune.uniform, g);
-    if (L.n == 0) return;
-    if (V == 2)
-      launch_ru<2, kFast7>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny,
-                           L, f, remap, tune.uniform, g);
-    else
-      launch_ru<1, kFast7>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx, ny,
-                           L, f, remap, tune.uniform, g);
-  } else {
-    if (faces)
-      launch_faces<kCanonical3>(face, nface, tune.chunk_z, s, tune.nontemporal, T2, T, iCp, nx,
-                                ny, c, tune.uniform, tune.uniform_value);
-    if (L.n == 0) return;
-    if (V == 2)
-      launch_ru<2, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
-                                ny, L, c, remap, tune.uniform, tune.uniform_value);
-    else
-      launch_ru<1, kCanonical3>(tune.rows, tune.unroll, grid, s, tune.nontemporal, T2, T, iCp, nx,
-                                ny, L, c, remap, tune.uniform, tune.uniform_value);
-  }
-  RMA_HIP_LAUNCH_CHECK();
+  // 32 planes per task (measured, profiles/diffusion3d.md: 3-8 % ahead of 128
+  // at 1024^3 and 1536^3, level at 512^3)
+  const int64_t total =
+      plan_boxes(L, sp.wide, sp.thin, sp.nwide, 1, V, tune.rows, tune.chunk_z, 32);
+  if (L.n == 0 && !sp.faces()) return;
+  const dim3 grid = grid_of(total), block(kBlock);
+  hipStream_t s = as_stream(stream);
+  const int nt = tune.nontemporal, remap = tune.xcd_remap ? 1 : 0;
+  with_arith3(c, tune, [&](auto a, const auto& k, double fac) {
+    constexpr int A = decltype(a)::value;
+    // the face boxes, one launch per lanes-per-row class in use (a wave task is
+    // 64/LX rows), ahead of the march of the rest
+    for_face_classes(sp, [&](auto lx, const Box* face, int nface) {
+      constexpr int LX = decltype(lx)::value;
+      FaceList F{};
+      const dim3 fgrid = grid_of(plan_faces(F, face, nface, 1, kWave / LX, 1, tune.chunk_z));
+      with_access3<false>(nt, tune.uniform, [&](auto nts, auto, auto uni) {
+        constexpr bool NTS = decltype(nts)::value, Uni = decltype(uni)::value;
+        stencil3d_xface_kernel<LX, NTS, Uni, A>
+            <<<fgrid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, F, k);
+      });
+      RMA_HIP_LAUNCH_CHECK();
+    });
+    if (L.n == 0) return;  // face boxes only: checked above
+    with_value<1, 2>(V, [&](auto v) {
+      with_rows_unroll(tune.rows, tune.unroll, [&](auto r, auto u) {
+        with_access3<true>(nt, tune.uniform, [&](auto nts, auto ntl, auto uni) {
+          constexpr bool Uni = decltype(uni)::value;
+          stencil3d_march_kernel<decltype(v)::value, decltype(r)::value, decltype(u)::value,
+                                 decltype(nts)::value, decltype(ntl)::value, Uni, A>
+              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, L, k, remap);
+        });
+      });
+    });
+    RMA_HIP_LAUNCH_CHECK();
+  });
 }
 
 }  // namespace rma

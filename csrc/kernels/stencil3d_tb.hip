@@ -59,7 +59,7 @@
 
 #include "rma/hip_check.h"
 #include "rma/kernels.h"
-#include "stencil_device.h"
+#include "stencil3d_device.h"
 
 namespace rma {
 namespace {
@@ -69,56 +69,16 @@ using namespace march;
 constexpr int kTbDefaultRows = 4;
 constexpr int64_t kTbDefaultChunkZ = 32;
 
-struct BoxListK {
-  Box b[kMaxBoxes];
-  int64_t xa[kMaxBoxes];         // origin of strip 0 (a multiple of V)
-  int64_t strips[kMaxBoxes];
-  int64_t bands[kMaxBoxes];
-  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / waves per block)
-  int64_t chunk_z[kMaxBoxes];    // output planes per task
-  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
-  int n;
-};
-
-__device__ __forceinline__ double cell3k(double xl, double c, double xr, double up, double dn,
-                                         double bk, double fr, double ic,
-                                         const StencilCoef3& k) {
-  const double qxR = (k.mlam * (xr - c)) * k.rdx;
-  const double qxL = (k.mlam * (c - xl)) * k.rdx;
-  const double qyU = (k.mlam * (dn - c)) * k.rdy;
-  const double qyD = (k.mlam * (c - up)) * k.rdy;
-  const double qzF = (k.mlam * (fr - c)) * k.rdz;
-  const double qzB = (k.mlam * (c - bk)) * k.rdz;
-  return c + k.dt * (ic * (((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy) - (qzF - qzB) * k.rdz));
-}
-
-// the update of one cell in arithmetic A (f: 1/Cp of the cell, or what Factor<true> holds)
-template <int A, bool Uni>
-__device__ __forceinline__ double update3k(double xl, double c, double xr, double up, double dn,
-                                           double bk, double fr, double f, const Coef3<A>& k) {
-  if constexpr (A == kFast7) return cell7<Uni>(xl, c, xr, up, dn, bk, fr, f, k);
-  else return cell3k(xl, c, xr, up, dn, bk, fr, f, k);
-}
-
-// 1/Cp as the kernel takes it: the array, or with Uni its one value (fast7: gs
-// times that value)
-template <bool Uni>
-using Factor = std::conditional_t<Uni, double, const double* __restrict__>;
-
 template <int K, int V, int R, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3>
 __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict__ T2,
                                                               const double* __restrict__ T,
                                                               Factor<Uni> iCp,
                                                               int64_t nx, int64_t ny, int64_t nz,
-                                                              BoxListK L, Coef3<A> k,
+                                                              BoxList L, Coef3<A> k,
                                                               int remap) {
   constexpr int NR = R + 2 * K;                 // rows of the level-0 window
   constexpr int64_t kStep = kWave * V - 2 * (K - 1);  // strip advance
-  const int64_t b = remap ? xcd_remap(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int bi = 0;
-  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
-  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const auto [bi, lb, wave] = locate_block(L, remap);
   const Box box = L.b[bi];
   const int64_t plane = nx * ny;
   // block lb of a box: strip fastest, then the group of 4 bands, then the z chunk
@@ -212,8 +172,8 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
           const double c = v == V - 1 ? right : cu[v == V - 1 ? v : v + 1];
           double f;
           if constexpr (Uni) f = iCp; else f = ic[l - 1][j][v];
-          res[v] = update3k<A, Uni>(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v],
-                                    Lv[l - 1][2][j][v], f, k);
+          res[v] = update3<A, Uni>(a, cu[v], c, up[v], dn[v], Lv[l - 1][0][j][v],
+                                   Lv[l - 1][2][j][v], f, k);
         }
         if (l < K) {
 #pragma unroll
@@ -242,33 +202,6 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
           for (int v = 0; v < V; ++v) ic[l][j][v] = ic[l - 1][j][v];
     }
   }
-}
-
-int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, int R,
-                     int chunk_z) {
-  L = BoxListK{};
-  int64_t total = 0;
-  const int64_t step = (int64_t)kWave * V - 2 * (K - 1);
-  for (int i = 0; i < nboxes; ++i) {
-    const Box& b = boxes[i];
-    if (b.empty()) continue;
-    const int n = L.n++;
-    L.b[n] = b;
-    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
-    // strip 0 starts K-1 columns left of the box (its first valid column), on a
-    // multiple of V and never left of the array (valid from the face on there)
-    const int64_t x0 = std::max<int64_t>(b.x0 - (K - 1), 0);
-    L.xa[n] = x0 - (x0 % V);
-    const int64_t first = L.xa[n] == 0 ? 0 : L.xa[n] + (K - 1);  // first valid column
-    L.strips[n] = std::max<int64_t>(1, (b.x1 - first + step - 1) / step);
-    L.bands[n] = (nyb + R - 1) / R;
-    L.groups[n] = (L.bands[n] + kWavesPerBlock - 1) / kWavesPerBlock;
-    // each chunk re-reads 2K planes and recomputes K-1
-    L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : kTbDefaultChunkZ, nzb);
-    total += L.strips[n] * L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
-    L.block_end[n] = total;
-  }
-  return total;
 }
 
 // ---------------------------------------------------------------------------
@@ -308,11 +241,11 @@ int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, in
 //     rows [l, NR-l) cover what the R output rows need; rows and planes on or
 //     past a face keep the lower level, so their clamped copies are never read
 //     through. A masked group computes on clamped loads and stores nothing.
-//   * Block list as FaceList in stencil3d.hip: groups of wave bands fastest, then
+//   * Block list: FaceList of stencil3d_device.h, groups of wave bands fastest, then
 //     the z chunk. One launch per lanes-per-segment class in use, on the same
 //     stream ahead of the march of the remaining boxes. No LDS, no barrier, no
 //     atomics; all offsets 64-bit.
-//   * The same update3k expression in the same order: bitwise the strip march's
+//   * The same update3 expression in the same order: bitwise the strip march's
 //     cells. T2 stores follow tb_nontemporal bit 0; bit 1 (non-temporal 1/Cp
 //     loads) is not instantiated for this path, which keeps it at 48
 //     instantiations: 1/Cp loads are plain, the measured default of the march.
@@ -330,32 +263,17 @@ int64_t plan_boxes_k(BoxListK& L, const Box* boxes, int nboxes, int K, int V, in
 // launcher splits the box list on the host; the strip march is untouched).
 // ---------------------------------------------------------------------------
 constexpr int kTbFaceDefaultRows = 2;
-constexpr int64_t kTbFaceDefaultChunkZ = 16;
-
-struct FaceListK {
-  Box b[kMaxBoxes];
-  int64_t xs[kMaxBoxes];         // first column of the segment
-  int64_t bands[kMaxBoxes];      // group tasks along y: ceil(rows / R)
-  int64_t groups[kMaxBoxes];     // blocks along y: ceil(bands / (RG * waves per block))
-  int64_t chunk_z[kMaxBoxes];    // output planes per task
-  int64_t block_end[kMaxBoxes];  // inclusive prefix sum of blocks
-  int n;
-};
 
 template <int K, int LX, int R, bool NTS, bool Uni, int A>
 __global__ __launch_bounds__(kBlock) void stencil3d_tb_xface_kernel(double* __restrict__ T2,
                                                                     const double* __restrict__ T,
                                                                     Factor<Uni> iCp, int64_t nx,
                                                                     int64_t ny, int64_t nz,
-                                                                    FaceListK L, Coef3<A> k) {
+                                                                    FaceList L, Coef3<A> k) {
   static_assert(LX == 8 || LX == 16 || LX == 32, "lanes per segment");
   constexpr int RG = kWave / LX;  // groups of a wave
   constexpr int NR = R + 2 * K;   // rows of the level-0 window
-  const int64_t b = blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int bi = 0;
-  while (bi < L.n - 1 && b >= L.block_end[bi]) ++bi;  // block-uniform, <= 8 steps
-  const int64_t lb = b - (bi ? L.block_end[bi - 1] : 0);
+  const auto [bi, lb, wave] = locate_block(L, 0);
   const Box box = L.b[bi];
   const int64_t plane = nx * ny;
   // block lb of a box: the group of 4 wave bands fastest, then the z chunk
@@ -437,18 +355,13 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_xface_kernel(double* __re
         }
         double f;
         if constexpr (Uni) f = iCp; else f = ic[l - 1][j];
-        const double res = update3k<A, Uni>(left, cu, right, Lv[l - 1][1][j - 1],
-                                            Lv[l - 1][1][j + 1], Lv[l - 1][0][j],
-                                            Lv[l - 1][2][j], f, k);
+        const double res = update3<A, Uni>(left, cu, right, Lv[l - 1][1][j - 1],
+                                           Lv[l - 1][1][j + 1], Lv[l - 1][0][j],
+                                           Lv[l - 1][2][j], f, k);
         if (l < K) {
           Lv[l < K ? l : 0][2][j] = (zface || rface[j] || xface) ? cu : res;
         } else if (m && j - K < nrows) {
-          double* q = T2 + z * plane + row[j] + x;
-          if constexpr (NTS) {
-            __builtin_nontemporal_store(res, q);
-          } else {
-            *q = res;
-          }
+          store1<NTS>(T2 + z * plane + row[j] + x, res);
         }
       }
     }
@@ -468,120 +381,6 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_xface_kernel(double* __re
   }
 }
 
-int64_t plan_faces_k(FaceListK& L, const Box* boxes, int nboxes, int K, int LX, int R,
-                     int chunk_z) {
-  L = FaceListK{};
-  int64_t total = 0;
-  const int64_t rg = kWave / LX;
-  for (int i = 0; i < nboxes; ++i) {
-    const Box& b = boxes[i];
-    const int n = L.n++;
-    L.b[n] = b;
-    const int64_t nzb = b.z1 - b.z0, nyb = b.y1 - b.y0;
-    // the segment starts K-1 columns left of the box (its first valid lane) and
-    // never left of the array (valid from the face on there)
-    L.xs[n] = std::max<int64_t>(b.x0 - (K - 1), 0);
-    L.bands[n] = (nyb + R - 1) / R;
-    const int64_t wbands = (L.bands[n] + rg - 1) / rg;
-    L.groups[n] = (wbands + kWavesPerBlock - 1) / kWavesPerBlock;
-    // each chunk re-reads 2K planes and recomputes K-1
-    L.chunk_z[n] = std::min<int64_t>(chunk_z > 0 ? chunk_z : kTbFaceDefaultChunkZ, nzb);
-    total += L.groups[n] * ((nzb + L.chunk_z[n] - 1) / L.chunk_z[n]);
-    L.block_end[n] = total;
-  }
-  return total;
-}
-
-template <int K, int LX, int R, int A>
-void launch_face_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
-                    const double* iCp, int64_t nx, int64_t ny, int64_t nz, const FaceListK& L,
-                    const Coef3<A>& c, bool uni, double fac) {
-  const dim3 block(kBlock);
-  if (uni) {
-    if (nt & 1)
-      stencil3d_tb_xface_kernel<K, LX, R, true, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
-                                                                               nz, L, c);
-    else
-      stencil3d_tb_xface_kernel<K, LX, R, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
-                                                                                nz, L, c);
-  } else if (nt & 1) {
-    stencil3d_tb_xface_kernel<K, LX, R, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny,
-                                                                              nz, L, c);
-  } else {
-    stencil3d_tb_xface_kernel<K, LX, R, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny,
-                                                                               nz, L, c);
-  }
-}
-
-// the face boxes of one launch, one kernel launch per lanes-per-segment class in use
-template <int K, int A>
-void launch_faces_k(const Box (&face)[3][kMaxBoxes], const int (&nface)[3], int R, int chunk_z,
-                    hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-                    int64_t nx, int64_t ny, int64_t nz, const Coef3<A>& c, bool uni, double fac) {
-  for (int cls = 0; cls < 3; ++cls) {
-    if (!nface[cls]) continue;
-    FaceListK L{};
-    const int64_t total = plan_faces_k(L, face[cls], nface[cls], K, 8 << cls, R, chunk_z);
-    RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
-    const dim3 grid((unsigned)total);
-#define RMA_TB_FACE(LX)                                                                         \
-  (R == 2 ? launch_face_nt<K, LX, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, uni, fac)    \
-          : launch_face_nt<K, LX, 4, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, uni, fac))
-    if (cls == 0) RMA_TB_FACE(8);
-    else if (cls == 1) RMA_TB_FACE(16);
-    else RMA_TB_FACE(32);
-#undef RMA_TB_FACE
-    RMA_HIP_LAUNCH_CHECK();
-  }
-}
-
-template <int K, int V, int R, int A>
-void launch_nt(dim3 grid, hipStream_t s, int nt, double* T2, const double* T, const double* iCp,
-               int64_t nx, int64_t ny, int64_t nz, const BoxListK& L, const Coef3<A>& c,
-               int remap, bool uni, double fac) {
-  const dim3 block(kBlock);
-  if (uni) {  // the 1/Cp-load bit has nothing to act on
-    if (nt & 1)
-      stencil3d_tb_kernel<K, V, R, true, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
-                                                                             nz, L, c, remap);
-    else
-      stencil3d_tb_kernel<K, V, R, false, false, true, A><<<grid, block, 0, s>>>(T2, T, fac, nx, ny,
-                                                                              nz, L, c, remap);
-    return;
-  }
-  switch (nt & 3) {
-    case 0:
-      stencil3d_tb_kernel<K, V, R, false, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
-                                                                        c, remap);
-      break;
-    case 1:
-      stencil3d_tb_kernel<K, V, R, true, false, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
-                                                                       c, remap);
-      break;
-    case 2:
-      stencil3d_tb_kernel<K, V, R, false, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
-                                                                       c, remap);
-      break;
-    default:
-      stencil3d_tb_kernel<K, V, R, true, true, false, A><<<grid, block, 0, s>>>(T2, T, iCp, nx, ny, nz, L,
-                                                                      c, remap);
-  }
-}
-
-template <int K, int A>
-void launch_k(int V, int R, dim3 grid, hipStream_t s, int nt, double* T2, const double* T,
-              const double* iCp, int64_t nx, int64_t ny, int64_t nz, const BoxListK& L,
-              const Coef3<A>& c, int remap, bool uni, double fac) {
-  if (V == 2 && R == 2)
-    launch_nt<K, 2, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
-  else if (V == 2)
-    launch_nt<K, 2, 4, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
-  else if (R == 2)
-    launch_nt<K, 1, 2, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
-  else
-    launch_nt<K, 1, 4, A>(grid, s, nt, T2, T, iCp, nx, ny, nz, L, c, remap, uni, fac);
-}
-
 }  // namespace
 
 bool stencil3dk_has(int K) { return K == 1 || K == 2; }
@@ -598,55 +397,51 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
   validate_boxes(T2, T, nx, ny, nz, boxes, nboxes);
   const int R = tune.tb_rows > 0 ? tune.tb_rows : kTbDefaultRows;
   RMA_CHECK_ARG(stencil3dk_has_rows(R), "tb_rows=" << tune.tb_rows << " (0: default, 2 or 4)");
-  RMA_CHECK_ARG(tune.vec == 1 || tune.vec == 2, "vec=" << tune.vec << " (1 or 2)");
-  RMA_CHECK_ARG(tune.tb_nontemporal >= 0 && tune.tb_nontemporal <= 3,
-                "tb_nontemporal=" << tune.tb_nontemporal << " (bits 0 and 1)");
-  RMA_CHECK_ARG(tune.tb_chunk_z >= 0, "tb_chunk_z=" << tune.tb_chunk_z);
-  RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
-                "fast_math: fast7 needs lam != 0 and finite coefficients");
-  // plan_dispatch3d (kernel_select.cpp) checks tune.xface and decides the path of
-  // every box: face boxes leave the list for the x-face kernel, launched first on
-  // the same stream, the rest keep their order in the strip march. xface = 0 has
-  // no face boxes: the caller's list, launch for launch.
-  Dispatch3D path[kMaxBoxes];
-  plan_dispatch3d(K, boxes, nboxes, tune, path);
-  Box wide[kMaxBoxes], face[3][kMaxBoxes];
-  int nwide = 0, nface[3] = {0, 0, 0};
-  for (int i = 0; i < nboxes; ++i) {
-    if (path[i].path == kPathXface) {
-      const int cls = path[i].lanes == 8 ? 0 : path[i].lanes == 16 ? 1 : 2;
-      face[cls][nface[cls]++] = boxes[i];
-    } else if (path[i].path != kPathNone) {
-      wide[nwide++] = boxes[i];
-    }
-  }
-  const bool faces = nface[0] + nface[1] + nface[2] > 0;
+  check_tuning3d(tune, c, "tb_", tune.tb_nontemporal, tune.tb_chunk_z);
+  // split_boxes3d (kernel_select.cpp) checks tune.xface and sorts the boxes by
+  // plan_dispatch3d's path: face boxes leave the list for the x-face kernel,
+  // launched first on the same stream, the rest keep their order in the strip
+  // march. xface = 0 has no face boxes: the caller's list, launch for launch.
+  const Split3D sp = split_boxes3d(K, boxes, nboxes, tune);
   const int Rf = tune.tb_rows > 0 ? tune.tb_rows : kTbFaceDefaultRows;
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
-  BoxListK L{};
-  const int64_t total = plan_boxes_k(L, wide, nwide, K, V, R, tune.tb_chunk_z);
-  if (L.n == 0 && !faces) return;
-  RMA_CHECK_ARG(total < (int64_t(1) << 31), "grid too large: " << total << " blocks");
+  BoxList L{};
+  const int64_t total =
+      plan_boxes(L, sp.wide, sp.thin, sp.nwide, K, V, R, tune.tb_chunk_z, kTbDefaultChunkZ);
+  if (L.n == 0 && !sp.faces()) return;
+  const dim3 grid = grid_of(total), block(kBlock);
   hipStream_t s = as_stream(stream);
-  if (tune.fast_math) {  // the uniform variant takes g = gs * value, formed here
-    const Fast7 f = fast7_constants(c);
-    const double g = f.gs * tune.uniform_value;
-    if (faces)
-      launch_faces_k<2, kFast7>(face, nface, Rf, tune.tb_chunk_z, s, tune.tb_nontemporal, T2, T,
-                                iCp, nx, ny, nz, f, tune.uniform, g);
-    if (L.n == 0) return;
-    launch_k<2, kFast7>(V, R, dim3((unsigned)total), s, tune.tb_nontemporal, T2, T, iCp, nx, ny,
-                        nz, L, f, tune.xcd_remap ? 1 : 0, tune.uniform, g);
-  } else {
-    if (faces)
-      launch_faces_k<2, kCanonical3>(face, nface, Rf, tune.tb_chunk_z, s, tune.tb_nontemporal, T2,
-                                     T, iCp, nx, ny, nz, c, tune.uniform, tune.uniform_value);
-    if (L.n == 0) return;
-    launch_k<2, kCanonical3>(V, R, dim3((unsigned)total), s, tune.tb_nontemporal, T2, T, iCp, nx,
-                             ny, nz, L, c, tune.xcd_remap ? 1 : 0, tune.uniform,
-                             tune.uniform_value);
-  }
-  RMA_HIP_LAUNCH_CHECK();
+  const int nt = tune.tb_nontemporal, remap = tune.xcd_remap ? 1 : 0;
+  with_arith3(c, tune, [&](auto a, const auto& k, double fac) {
+    constexpr int A = decltype(a)::value;
+    // the face boxes, one launch per lanes-per-segment class in use (a wave runs
+    // 64/LX group tasks of Rf rows), ahead of the march of the rest
+    for_face_classes(sp, [&](auto lx, const Box* face, int nface) {
+      constexpr int LX = decltype(lx)::value;
+      FaceList F{};
+      const dim3 fgrid = grid_of(plan_faces(F, face, nface, K, Rf, kWave / LX, tune.tb_chunk_z));
+      with_value<2, 4>(Rf, [&](auto r) {
+        with_access3<false>(nt, tune.uniform, [&](auto nts, auto, auto uni) {
+          constexpr bool NTS = decltype(nts)::value, Uni = decltype(uni)::value;
+          stencil3d_tb_xface_kernel<2, LX, decltype(r)::value, NTS, Uni, A>
+              <<<fgrid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, nz, F, k);
+        });
+      });
+      RMA_HIP_LAUNCH_CHECK();
+    });
+    if (L.n == 0) return;  // face boxes only: checked above
+    with_value<1, 2>(V, [&](auto v) {
+      with_value<2, 4>(R, [&](auto r) {
+        with_access3<true>(nt, tune.uniform, [&](auto nts, auto ntl, auto uni) {
+          constexpr bool Uni = decltype(uni)::value;
+          stencil3d_tb_kernel<2, decltype(v)::value, decltype(r)::value, decltype(nts)::value,
+                              decltype(ntl)::value, Uni, A>
+              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, nz, L, k, remap);
+        });
+      });
+    });
+    RMA_HIP_LAUNCH_CHECK();
+  });
 }
 
 }  // namespace rma

@@ -219,31 +219,6 @@ __device__ __forceinline__ double cell(double xl, double c, double xr, double up
   return c + k.dt * (ic * ((-(qxR - qxL)) * k.rdx - (qyU - qyD) * k.rdy));
 }
 
-// The fast7 cell update of the 3D kernels (rma/kernels.h): the 7-point sum, the
-// constants folded on the host. The fmas are explicit (contraction is off), so
-// std::fma on the host is a bitwise twin. f is 1/Cp of the cell (g = gs*f, one
-// rounded multiply) or, with Uni, the product gs*value formed on the host.
-template <bool Uni>
-__device__ __forceinline__ double cell7(double xl, double c, double xr, double up, double dn,
-                                        double bk, double fr, double f, const Fast7& k) {
-  double g;
-  if constexpr (Uni) g = f; else g = k.gs * f;
-  const double sx = xr + xl;
-  const double sy = up + dn;
-  const double sz = bk + fr;
-  double t = __builtin_fma(k.mkc, c, sx);
-  t = __builtin_fma(k.ry, sy, t);
-  t = __builtin_fma(k.rz, sz, t);
-  return __builtin_fma(g, t, c);
-}
-
-// Arithmetic of a 3D kernel instantiation and the coefficients it takes as its
-// kernel argument: canonical the StencilCoef3 itself, fast7 the folded constants.
-constexpr int kCanonical3 = 0;
-constexpr int kFast7 = 1;
-template <int A>
-using Coef3 = std::conditional_t<A == kFast7, Fast7, StencilCoef3>;
-
 template <int V>
 __device__ __forceinline__ void row_update(double (&res)[V], const double (&up)[V],
                                            const double (&cu)[V], const double (&dn)[V],

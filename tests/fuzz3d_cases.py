@@ -259,8 +259,8 @@ def twin(c):
 
 
 def march_strips(K, V, x0, x1):
-    """Strips the launchers give a march box (plan_boxes / plan_boxes_k in
-    csrc/kernels/stencil3d*.hip); for the coverage counts only."""
+    """Strips the launchers give a march box (plan_boxes in
+    csrc/kernels/stencil3d_device.h); for the coverage counts only."""
     if K == 1:
         sw = 64 * V
         return -(-(x1 - (x0 - x0 % sw)) // sw)

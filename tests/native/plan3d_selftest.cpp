@@ -1,4 +1,5 @@
-// Stand-alone self test of the 3D pass geometry (csrc/runtime/plan3d.cpp), built
+// Stand-alone self test of the 3D pass geometry (csrc/runtime/plan3d.cpp) and of
+// the launchers' box split (split_boxes3d, csrc/kernels/kernel_select.cpp), built
 // with -fsanitize=address,undefined by tests/test_plan3d_host_sanitized_cpu.py.
 // The hand cases of tests/test_plan3d_cpu.py plus a sweep of small tiles; every
 // split is checked as a partition of the owned box on a cell count array.
@@ -6,6 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "rma/kernels.h"
 #include "rma/plan3d.h"
 
 using namespace rma;
@@ -94,6 +96,33 @@ int main() {
     refused = true;
   }
   CHECK(refused);
+  {  // split_boxes3d: empty, thin, march and the three face classes; every list
+     // keeps the input order, which fixes the launch order
+    const Box in[8] = {{1, 7, 1, 5, 1, 5},    {2, 2, 1, 5, 1, 5},    {1, 34, 1, 5, 1, 5},
+                       {3, 17, 1, 5, 1, 5},   {4, 34, 2, 5, 1, 5},   {5, 11, 1, 5, 1, 5},
+                       {6, 39, 1, 5, 1, 5},   {7, 21, 1, 5, 1, 5}};  // widths 6 0 33 14 30 6 33 14
+    auto is = [&](const Box& b, int i) { return same(b, in[i]); };
+    Stencil3DTuning tn;
+    Split3D s = split_boxes3d(1, in, 8, tn);  // xface = 0: widths up to 8 thin, the rest march
+    CHECK(!s.faces() && s.nwide == 7);
+    const int w0[7] = {0, 2, 3, 4, 5, 6, 7};
+    for (int i = 0; i < 7; ++i) CHECK(is(s.wide[i], w0[i]) && s.thin[i] == (w0[i] == 0 || w0[i] == 5));
+    tn.xface = 32;
+    s = split_boxes3d(1, in, 8, tn);  // K = 1: 6 -> 8 lanes, 14 -> 16, 30 -> 32, 33 marches
+    CHECK(s.nwide == 2 && is(s.wide[0], 2) && is(s.wide[1], 6) && !s.thin[0] && !s.thin[1]);
+    CHECK(s.nface[0] == 2 && is(s.face[0][0], 0) && is(s.face[0][1], 5));
+    CHECK(s.nface[1] == 2 && is(s.face[1][0], 3) && is(s.face[1][1], 7));
+    CHECK(s.nface[2] == 1 && is(s.face[2][0], 4));
+    s = split_boxes3d(2, in, 8, tn);  // K = 2 needs W + 2 lanes: the same classes
+    CHECK(s.nwide == 2 && is(s.wide[0], 2) && is(s.wide[1], 6) && !s.thin[0] && !s.thin[1]);
+    CHECK(s.nface[0] == 2 && is(s.face[0][0], 0) && is(s.face[0][1], 5));
+    CHECK(s.nface[1] == 2 && is(s.face[1][0], 3) && is(s.face[1][1], 7));
+    CHECK(s.nface[2] == 1 && is(s.face[2][0], 4));
+    tn.xface = 14;
+    s = split_boxes3d(2, in, 8, tn);  // width 30 is past xface: it marches, no thin path at K = 2
+    CHECK(s.nwide == 3 && is(s.wide[0], 2) && is(s.wide[1], 4) && is(s.wide[2], 6));
+    CHECK(!s.thin[0] && !s.thin[1] && !s.thin[2] && s.nface[0] == 2 && s.nface[1] == 2 && !s.nface[2]);
+  }
   std::printf("plan3d selftest OK (%d splits)\n", splits);
   return 0;
 }

@@ -17,6 +17,7 @@ def test_plan3d_selftest_asan_ubsan(tmp_path):
     exe = tmp_path / "plan3d_selftest"
     srcs = [os.path.join(ROOT, "tests", "native", "plan3d_selftest.cpp"),
             os.path.join(ROOT, "csrc", "runtime", "plan3d.cpp"),
+            os.path.join(ROOT, "csrc", "kernels", "kernel_select.cpp"),
             os.path.join(ROOT, "csrc", "runtime", "errors.cpp")]
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
