@@ -41,7 +41,10 @@ dispatch) and its x-face path at rows per group 2 and 4 and every
 (0,0,0) (no exchange: the floor), ``perf`` with periods (1,1,1) (the rank is its own
 neighbour on all six sides) and ``perf_hide`` with periods (1,1,1), with the x-face
 path off and on (one- and two-step frames alike), every model rebuilt in every round
-so the rounds interleave.
+so the rounds interleave. ``--hide --fused`` adds ``perf_hide`` with frame-first
+single-launch passes (``Diffusion3DConfig.fused``) as a fifth column and reports
+``vs_split`` / ``vs_split_xface`` = the split column's median / the fused median
+(profiles/diffusion3d_fused.md).
 ``recovered`` = (perf periodic - perf_hide) / (perf periodic - perf open). It
 combines with ``--temporal 2``, ``--uniform`` (1/Cp one value: the model's scan
 finds it; without the flag the scan is disabled) and ``--fast-math``
@@ -301,6 +304,8 @@ def sweep_hide(n: int, a) -> dict:
     cases = {"perf_open": ("perf", (0, 0, 0), 0), "perf_periodic": ("perf", (1, 1, 1), 0),
              "hide_periodic": ("perf_hide", (1, 1, 1), 0),
              "hide_periodic_xface": ("perf_hide", (1, 1, 1), None)}
+    if a.fused:
+        cases["hide_periodic_fused"] = ("perf_hide", (1, 1, 1), 0)
     steps = a.iters * a.temporal
     times = {k: [] for k in cases}
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -309,7 +314,8 @@ def sweep_hide(n: int, a) -> dict:
             m = Diffusion3D(Diffusion3DConfig(
                 variant=variant, nx=n, ny=n, nz=n, nt=steps, init="random", periods=periods,
                 quiet=True, temporal=a.temporal, fast_math=a.fast_math,
-                uniform_factor=a.uniform, b_width=a.b_width, xface=xface))
+                uniform_factor=a.uniform, b_width=a.b_width, xface=xface,
+                fused=k.endswith("_fused")))
             m.step(2 * a.temporal)
             m.synchronize()
             ev0.record()
@@ -318,16 +324,21 @@ def sweep_hide(n: int, a) -> dict:
             ev1.synchronize()
             if rnd:
                 times[k].append(ev0.elapsed_time(ev1) / steps)
+            m.synchronize()  # raises if a fused pass's wait timed out
             m.close()
             del m
     torch.cuda.empty_cache()
     res = _summary(times)
     exposed = res["perf_periodic"]["median_ms"] - res["perf_open"]["median_ms"]
-    for k in ("hide_periodic", "hide_periodic_xface"):
+    for k in [c for c in cases if c.startswith("hide_")]:
         gain = res["perf_periodic"]["median_ms"] - res[k]["median_ms"]
         res[k]["gain_ms"] = gain
         res[k]["recovered"] = gain / exposed if exposed > 0 else float("nan")
     res["perf_periodic"]["exposed_ms"] = exposed
+    if a.fused:
+        f = res["hide_periodic_fused"]
+        f["vs_split"] = res["hide_periodic"]["median_ms"] / f["median_ms"]
+        f["vs_split_xface"] = res["hide_periodic_xface"]["median_ms"] / f["median_ms"]
     return res
 
 
@@ -423,6 +434,8 @@ def main(argv=None) -> int:
                     help="widths of an x-face box pair: today's dispatch, the x-face path, z slabs")
     ap.add_argument("--hide", action="store_true",
                     help="Diffusion3D perf (open, periodic) against perf_hide (periodic)")
+    ap.add_argument("--fused", action="store_true",
+                    help="--hide: also perf_hide with frame-first single-launch passes")
     ap.add_argument("--native", action="store_true",
                     help="Diffusion3D's Python-issued loop against the native loop (perf, "
                          "perf_hide; periodic, uniform 1/Cp): ms per step and host enqueue time")
@@ -445,6 +458,8 @@ def main(argv=None) -> int:
                       + (f"  exposed exchange {v['exposed_ms']:.4f} ms" if "exposed_ms" in v else "")
                       + (f"  gain {v['gain_ms']:.4f} ms, recovered {v['recovered']:.2f}"
                          if "recovered" in v else "")
+                      + (f"  {v['vs_split']:.3f} x split, {v['vs_split_xface']:.3f} x split+xface"
+                         if "vs_split" in v else "")
                       + (f"  enqueue {v['enqueue_ms']:.4f} ms/step (spread "
                          f"{v['enqueue_spread']:.3f})" if "enqueue_ms" in v else "")
                       + (f"  {v['vs_python']:.3f} x python (enqueue "

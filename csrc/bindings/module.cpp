@@ -220,10 +220,12 @@ PYBIND11_MODULE(_C, m) {
       [](uintptr_t T2, uintptr_t T, uintptr_t iCp, int64_t nx, int64_t ny, int64_t nz,
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, uintptr_t stream, bool gpu, bool uniform,
-         double uniform_value, bool fast_math, int xface) {
+         double uniform_value, bool fast_math, int xface, uintptr_t signal, int signal_boxes) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
+          tn.signal = P<uint64_t>(signal);
+          tn.signal_boxes = signal_boxes;
           tn.fast_math = fast_math ? 1 : 0;
           tn.xface = xface;
           tn.uniform = uniform;
@@ -251,7 +253,7 @@ PYBIND11_MODULE(_C, m) {
       py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
       py::arg("xcd_remap") = 1, py::arg("stream") = 0, py::arg("gpu") = true,
       py::arg("uniform") = false, py::arg("uniform_value") = 0.0, py::arg("fast_math") = false,
-      py::arg("xface") = 0);
+      py::arg("xface") = 0, py::arg("signal") = 0, py::arg("signal_boxes") = 0);
   m.def(
       "fast7_ok", [](const Coef5& coef) { return fast7_ok(to_coef3(coef)); }, py::arg("coef"));
   // cells per lane a GPU launch with these arrays runs (stencil3d_vec)
@@ -273,10 +275,12 @@ PYBIND11_MODULE(_C, m) {
          const std::vector<Box6>& boxes, const Coef5& coef, int rows, int unroll, int vec,
          int nontemporal, int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
          int tb_nontemporal, uintptr_t stream, bool gpu, bool uniform, double uniform_value,
-         bool fast_math, int xface) {
+         bool fast_math, int xface, uintptr_t signal, int signal_boxes) {
         auto b = to_boxes(boxes);
         if (gpu) {
           Stencil3DTuning tn;
+          tn.signal = P<uint64_t>(signal);
+          tn.signal_boxes = signal_boxes;
           tn.fast_math = fast_math ? 1 : 0;
           tn.xface = xface;
           tn.uniform = uniform;
@@ -308,7 +312,38 @@ PYBIND11_MODULE(_C, m) {
       py::arg("chunk_z") = 0, py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0,
       py::arg("tb_chunk_z") = 0, py::arg("tb_nontemporal") = 0, py::arg("stream") = 0,
       py::arg("gpu") = true, py::arg("uniform") = false, py::arg("uniform_value") = 0.0,
-      py::arg("fast_math") = false, py::arg("xface") = 0);
+      py::arg("fast_math") = false, py::arg("xface") = 0, py::arg("signal") = 0,
+      py::arg("signal_boxes") = 0);
+  // The march launch of a K-step pass with these boxes, V cells per lane, by the
+  // function both launchers run (stencil3d_fused_plan; host only): (blocks,
+  // prefix_blocks, signalling_waves, boxes of the launch, [(box, local block), ...]
+  // per block). signal_boxes > 0: the signalling launch, with every launcher check.
+  m.def(
+      "stencil3d_fused_plan",
+      [](int K, int V, const std::vector<Box6>& boxes, int signal_boxes, int rows, int unroll,
+         int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z, int xface) {
+        auto b = to_boxes(boxes);
+        Stencil3DTuning tn;
+        tn.rows = rows;
+        tn.unroll = unroll;
+        tn.chunk_z = chunk_z;
+        tn.xcd_remap = xcd_remap;
+        tn.tb_rows = tb_rows;
+        tn.tb_chunk_z = tb_chunk_z;
+        tn.xface = xface;
+        RMA_CHECK_ARG(b.size() <= (size_t)kMaxBoxes,
+                      "nboxes=" << b.size() << " (at most " << kMaxBoxes << " boxes per launch)");
+        const Fused3DPlan p =
+            stencil3d_fused_plan(K, V, b.data(), (int)b.size(), tn, signal_boxes, nullptr);
+        std::vector<int64_t> map((size_t)(2 * p.blocks));
+        stencil3d_fused_plan(K, V, b.data(), (int)b.size(), tn, signal_boxes, map.data());
+        std::vector<std::pair<int64_t, int64_t>> pairs((size_t)p.blocks);
+        for (int64_t i = 0; i < p.blocks; ++i) pairs[(size_t)i] = {map[2 * i], map[2 * i + 1]};
+        return py::make_tuple(p.blocks, p.prefix_blocks, p.signalling_waves, p.boxes, pairs);
+      },
+      py::arg("K"), py::arg("V"), py::arg("boxes"), py::arg("signal_boxes"), py::arg("rows") = 4,
+      py::arg("unroll") = 2, py::arg("chunk_z") = 0, py::arg("xcd_remap") = 1,
+      py::arg("tb_rows") = 0, py::arg("tb_chunk_z") = 0, py::arg("xface") = 0);
   // the kernel path of every non-empty box of a K-step launch with this xface
   // (plan_dispatch3d, the rule both launchers run): [(path, lanes), ...] with path
   // "march", "thin" or "xface". Host only.
@@ -933,8 +968,10 @@ PYBIND11_MODULE(_C, m) {
                        bool fast_math, const std::array<int64_t, 3>& b_width, int xface,
                        bool uniform_factor, int rows, int unroll, int vec, int nontemporal,
                        int chunk_z, int xcd_remap, int tb_rows, int tb_chunk_z,
-                       int tb_nontemporal) {
+                       int tb_nontemporal, int fused, double fused_timeout_s) {
              Exec3DParams p;
+             p.fused = fused;
+             p.fused_timeout_s = fused_timeout_s;
              p.mode = mode;
              p.coef = to_coef3(coef);
              p.steps_per_pass = steps_per_pass;
@@ -966,7 +1003,8 @@ PYBIND11_MODULE(_C, m) {
            py::arg("uniform_factor") = true, py::arg("rows") = 4, py::arg("unroll") = 2,
            py::arg("vec") = 2, py::arg("nontemporal") = 3, py::arg("chunk_z") = 0,
            py::arg("xcd_remap") = 1, py::arg("tb_rows") = 0, py::arg("tb_chunk_z") = 0,
-           py::arg("tb_nontemporal") = 0, py::keep_alive<1, 10>())
+           py::arg("tb_nontemporal") = 0, py::arg("fused") = 0,
+           py::arg("fused_timeout_s") = 60.0, py::keep_alive<1, 10>())
       .def(
           "run", [](Diffusion3DExecutor& e, int64_t n, uintptr_t s) { e.run(n, S(s)); },
           py::arg("nsteps"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
@@ -977,6 +1015,9 @@ PYBIND11_MODULE(_C, m) {
            py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("steps_done", &Diffusion3DExecutor::steps_done)
       .def_property_readonly("passes_done", &Diffusion3DExecutor::passes_done)
+      .def_property_readonly("fused_passes", &Diffusion3DExecutor::fused_passes)
+      .def_property_readonly("fused_timeout_s", &Diffusion3DExecutor::fused_timeout_s)
+      .def("check", &Diffusion3DExecutor::check)
       .def_property_readonly("frame_xface", &Diffusion3DExecutor::frame_xface)
       .def("plan", &Diffusion3DExecutor::plan, py::arg("nsteps"));
 

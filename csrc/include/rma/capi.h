@@ -173,15 +173,32 @@ int rma_init_random3d(rma_grid* g, double* A, int64_t nx, int64_t ny, int64_t nz
  * After writing to iCp call rma_executor3d_rescan_factor. Bad arguments are
  * refused before any launch, named in rma_last_error. The executor pins its
  * grid like the 2D ones: finalize and destroy may come in any order.
- * Not here: hipGraph replay, frame-first fused passes, a pass planner,
- * direct-store halos, more than two steps per pass. */
+ * rma_executor3d_create_f adds fused (the 2D _k / _kf / _g naming):
+ * 0 = perf_hide's two launches on two streams, what rma_executor3d_create
+ * means; 1 = frame-first single-launch passes (mode 1 only): a pass that splits
+ * is one launch, the frame boxes dispatched first, whose last frame wave raises
+ * a device flag the exchange stream waits on (bounded by RMA_EXEC_FUSED_TIMEOUT,
+ * 60 s). The same field bit for bit. A wait that timed out fails the next
+ * rma_executor3d_run and rma_executor3d_check with the reason in rma_last_error,
+ * and is printed on stderr when the executor is destroyed. Other values of
+ * fused are refused.
+ * Not here: hipGraph replay, a pass planner, direct-store halos, more than two
+ * steps per pass. */
 typedef struct rma_executor3d rma_executor3d;
 int rma_executor3d_create(rma_grid* g, int mode, double* T, double* T2, const double* iCp,
                           int64_t nx, int64_t ny, int64_t nz, const double coef[5],
                           const int64_t b_width[3], int steps_per_pass, int fast_math, int xface,
                           rma_executor3d** out);
+int rma_executor3d_create_f(rma_grid* g, int mode, double* T, double* T2, const double* iCp,
+                            int64_t nx, int64_t ny, int64_t nz, const double coef[5],
+                            const int64_t b_width[3], int steps_per_pass, int fast_math,
+                            int xface, int fused, rma_executor3d** out);
 /* enqueue nsteps after the work on `stream`; `stream` waits for them (asynchronous) */
 int rma_executor3d_run(rma_executor3d* e, int64_t nsteps, void* stream);
+/* nonzero (the reason in rma_last_error) if a fused pass's wait has timed out */
+int rma_executor3d_check(rma_executor3d* e);
+/* passes enqueued as one frame-first launch so far */
+int64_t rma_executor3d_fused_passes(const rma_executor3d* e);
 /* 0: the field is in T, 1: in T2 */
 int rma_executor3d_parity(const rma_executor3d* e);
 /* nonzero: the last scan found one value in every cell of iCp */

@@ -25,12 +25,32 @@
 //               perf pass, kept ordered on H while another depth of the same run
 //               overlaps, on the caller's stream otherwise.
 //
+//   perf_hide, fused = 1 (frame-first single-launch passes): a pass that splits
+//               is ONE launch on L, the frame slabs as its signal prefix and the
+//               interior after them (Stencil3DTuning::signal); the last frame wave
+//               raises a device flag that H waits on:
+//                 H : ......[wait flag][lower flag][exchange(T2)]
+//                 L : [frame blocks | interior blocks ............]
+//               per pass, enqueued in this order: L waits for the event of H's
+//               previous exchange (the frame blocks read the halo); the launch on
+//               L; on H flag_wait_gpu(signal + 1, 1), flag_write_gpu(signal + 1, 0),
+//               the exchange of the new field, its event. The launch is always
+//               enqueued before the wait on it, so a wait depends only on work
+//               enqueued earlier. The flag is lowered before the next launch can
+//               start (that launch waits for this exchange), the counter is
+//               re-armed by the wave that raises the flag. In such a launch no
+//               box takes the x-face path. Passes that do not split stay the perf
+//               pass, ordered as above. The wait is bounded (fused_timeout_s);
+//               a timeout is recorded in a mapped host word and reported as an
+//               invalid argument by the next run(), by check() and at destruction
+//               (on stderr there: a destructor does not throw).
+//
 // run(n) plans n / K passes of K = steps_per_pass steps, then n % K one-step
 // passes. The exchange is the per-dimension one with exact corners.
 //
-// Out of scope (the 2D executor, rma/executor.h, has them): hipGraph replay,
-// frame-first single-launch passes, a pass planner, direct-store halos and
-// passes deeper than two steps.
+// Out of scope (the 2D executor, rma/executor.h, has them): hipGraph replay, a
+// pass planner, direct-store halos, passes deeper than two steps, and the x-face
+// path inside a fused launch.
 #pragma once
 
 #include <array>
@@ -59,6 +79,12 @@ struct Exec3DParams {
   // of the grid: overlap and halo width per dimension (x, y, z)
   std::array<int64_t, 3> overlaps{2, 2, 2};
   std::array<int64_t, 3> halowidths{1, 1, 1};
+  // perf_hide: 1 = frame-first single-launch passes (above), 0 = two launches on
+  // two streams. The default is decided by profiles/diffusion3d_fused.md.
+  int fused = 0;
+  // bound of the exchange stream's wait for the frame flag, seconds; the
+  // environment's RMA_EXEC_FUSED_TIMEOUT, where set, replaces it (as in 2D)
+  double fused_timeout_s = 60.0;
 };
 
 class Diffusion3DExecutor {
@@ -69,7 +95,9 @@ class Diffusion3DExecutor {
   // what is wrong): mode outside {0, 1}, steps_per_pass outside {1, 2}, an
   // extent < 3, along a dimension with a neighbour an overlap below 2K or a halo
   // width other than K, fast_math with coefficients that fail fast7_ok, a
-  // b_width < 1, xface outside -1..kXfaceMax, null or overlapping T / T2 / iCp.
+  // b_width < 1, xface outside -1..kXfaceMax, null or overlapping T / T2 / iCp,
+  // fused outside {0, 1}, fused = 1 with mode = perf or a tuning the signalling
+  // kernels are not instantiated for (rows 4, unroll 2, tb_rows 0 or 4).
   // Synchronises the device once (the 1/Cp scan) and prepares the exchanger's
   // pack buffers for both fields.
   Diffusion3DExecutor(double* T, double* T2, const double* iCp, int64_t nx, int64_t ny, int64_t nz,
@@ -86,6 +114,13 @@ class Diffusion3DExecutor {
   int parity() const { return parity_; }
   int64_t steps_done() const { return steps_; }
   int64_t passes_done() const { return passes_; }
+  // passes enqueued as one frame-first launch (fused = 1 and the pass splits)
+  int64_t fused_passes() const { return fused_passes_; }
+  double fused_timeout_s() const { return fused_timeout_s_; }
+  // Throws (an invalid argument) if a fused pass's wait for the frame flag has
+  // timed out since construction: the halos of that pass are wrong. run() calls
+  // it first; call it after synchronising to learn about the passes just run.
+  void check() const;
   // The verdict of the last scan of 1/Cp (count_differing_gpu): every cell holds
   // bit for bit one value, which the passes then take as a kernel argument
   // instead of reading the array. False with Exec3DParams::uniform_factor off
@@ -100,7 +135,7 @@ class Diffusion3DExecutor {
 
  private:
   void launch(int K, const Box* boxes, int n, bool frame, double* Tin, double* Tout,
-              stream_t s) const;
+              stream_t s, int signal_boxes = 0) const;
   void exchange(double* A, stream_t s);
   HaloField field(double* A) const;
   void scan_factor();
@@ -125,6 +160,11 @@ class Diffusion3DExecutor {
   int parity_ = 0;
   int64_t steps_ = 0;
   int64_t passes_ = 0;
+  int64_t fused_passes_ = 0;
+  double fused_timeout_s_ = 60.0;
+  uint64_t* sig_ = nullptr;        // device: [frame wave counter, frame flag], fused only
+  uint32_t* ferr_host_ = nullptr;  // mapped host word: 1 = a frame wait timed out
+  uint32_t* ferr_dev_ = nullptr;
 };
 
 }  // namespace rma

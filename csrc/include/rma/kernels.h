@@ -239,6 +239,21 @@ struct Stencil3DTuning {
   // march. 0: today's dispatch. Outside 0..kXfaceMax: an invalid argument before
   // any work. plan_dispatch3d below is the rule both launchers run.
   int xface = 0;
+  // Frame-first fused pass (the 2D fields of StencilTuning above, for boxes):
+  // signal != nullptr makes the blocks of the first signal_boxes non-empty boxes
+  // the signal prefix of the launch. They dispatch first (never XCD-remapped; the
+  // rest is remapped among itself) and every one of their waves counts its
+  // completion in signal[0] (device memory, zero); the last one resets the
+  // counter and stores 1 into signal[1] with system-scope release. A
+  // flag_wait_gpu(signal + 1, 1, ...) on another stream then orders work after
+  // those boxes without waiting for the rest of the launch. Needs
+  // 1 <= signal_boxes < the number of non-empty boxes and the shipped tuning
+  // (rows = 4, unroll = 2; tb_rows 0 or 4): anything else is an invalid argument
+  // before any work, as is signal_boxes != 0 without a signal. The x-face kernels
+  // do not signal: in a signalling launch every box runs the march or thin path
+  // and xface is not applied. Without a signal the launch is today's launch.
+  uint64_t* signal = nullptr;
+  int signal_boxes = 0;
 };
 constexpr int kXfaceMax = 32;
 
@@ -274,6 +289,23 @@ struct Split3D {
   bool faces() const { return nface[0] + nface[1] + nface[2] > 0; }
 };
 Split3D split_boxes3d(int K, const Box* boxes, int nboxes, const Stencil3DTuning& tune);
+// The march launch of a K-step pass at V cells per lane (stencil3d_vec), computed
+// on the host by the function both launchers run (stencil3d.hip; no GPU needed):
+// its blocks, the blocks of the signal prefix (the first signal_boxes non-empty
+// boxes; 0: an unsignalled launch, which applies tune.xface as usual and counts the
+// march launch only) and the waves that count in signal[0]. map != nullptr:
+// map[2 b], map[2 b + 1] = (box index among the launch's boxes, block inside the
+// box) of block b, by the function the signalling kernels run (block_after);
+// room for 2 * blocks entries, so call it once with nullptr. tune.signal is not
+// read: signal_boxes > 0 asks for the signalling plan with every launcher check.
+struct Fused3DPlan {
+  int64_t blocks = 0;
+  int64_t prefix_blocks = 0;
+  int64_t signalling_waves = 0;
+  int boxes = 0;  // boxes of the march launch
+};
+Fused3DPlan stencil3d_fused_plan(int K, int V, const Box* boxes, int nboxes,
+                                 const Stencil3DTuning& tune, int signal_boxes, int64_t* map);
 // is (rows, unroll) an instantiated march?
 bool stencil3d_has(int rows, int unroll);
 // Cells per lane both 3D launchers run: tune.vec with even nx and 16-byte

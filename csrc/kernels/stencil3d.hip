@@ -133,14 +133,21 @@ __device__ __forceinline__ void z_steps(double (&P)[NP][R][V], double* __restric
 // (8, 1) 161 / 3. fast7 with Uni: V = 2 (2, 1) 62 / 8, (2, 2) 104 / 4, (4, 1) 102 / 4,
 // (4, 2) 169 / 2, (8, 1) 183 / 2; V = 1 (2, 1) 50 / 8, (2, 2) 80 / 6, (4, 1) 70 / 7, (4, 2) 129 / 3,
 // (8, 1) 126-127 / 4.
-template <int V, int R, int U, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3>
+// Sig (Stencil3DTuning::signal, frame-first fused passes; stencil3d_device.h
+// SigArg): the blocks of the signal prefix keep dispatch order and each way out of
+// the kernel counts the wave. Instantiated for R = 4, U = 2 (the shipped tuning)
+// only. Without Sig sg is empty and this is the kernel it was: the 120
+// instantiations above keep their registers, scratch and occupancy
+// (profiles/diffusion3d_fused.md).
+template <int V, int R, int U, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3,
+          bool Sig = false>
 __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restrict__ T2,
                                                                  const double* __restrict__ T,
                                                                  Factor<Uni> iCp,
                                                                  int64_t nx, int64_t ny,
                                                                  BoxList L, Coef3<A> k,
-                                                                 int remap) {
-  const auto [bi, lb, wave] = locate_block(L, remap);
+                                                                 int remap, SigArg<Sig> sg) {
+  const auto [bi, lb, wave] = locate_block(L, remap, sg);
   const Box box = L.b[bi];
   const int64_t plane = nx * ny;
   if (L.chunk_z[bi] < 0) {
@@ -148,7 +155,10 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
     // would load up to 128 times the bytes it updates)
     const int64_t rows = box.y1 - box.y0;
     const int64_t i = lb * kBlock + threadIdx.x;
-    if (i >= rows * (box.z1 - box.z0)) return;
+    if (i >= rows * (box.z1 - box.z0)) {
+      if constexpr (Sig) sg.wave_done();  // counts only where the whole wave is past the box
+      return;
+    }
     const int64_t z = box.z0 + i / rows, y = box.y0 + i % rows;
     const int64_t o = z * plane + y * nx;
     for (int64_t x = box.x0; x < box.x1; ++x) {
@@ -164,6 +174,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
         T2[o + x] = v;
       }
     }
+    if constexpr (Sig) sg.wave_done();
     return;
   }
   // block lb of a box: strip fastest, then the group of 4 bands, then the z chunk
@@ -171,7 +182,10 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
   const int64_t rest = lb / L.strips[bi];
   const int64_t band = (rest % L.groups[bi]) * kWavesPerBlock + wave;
   const int64_t zc = rest / L.groups[bi];
-  if (band >= L.bands[bi]) return;  // the whole wave
+  if (band >= L.bands[bi]) {  // the whole wave
+    if constexpr (Sig) sg.wave_done();
+    return;
+  }
   const int64_t xs = L.xa[bi] + strip * (kWave * V);
   const int64_t ya = box.y0 + band * R;
   const int64_t za = box.z0 + zc * L.chunk_z[bi];
@@ -202,6 +216,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_march_kernel(double* __restr
   if constexpr (U > 1) {
     for (; z < zb; ++z) z_steps<V, R, 1, U + 2, NTS, NTL, Uni, A>(P, T2, T, iCp, t, z, k);
   }
+  if constexpr (Sig) sg.wave_done();
 }
 
 // ---------------------------------------------------------------------------
@@ -317,17 +332,18 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
                 "rows=" << tune.rows << " unroll=" << tune.unroll
                         << ": rows 2 or 4 with unroll 1 or 2, or rows 8 with unroll 1");
   check_tuning3d(tune, c, "", tune.nontemporal, tune.chunk_z);
-  // split_boxes3d (kernel_select.cpp) checks tune.xface and sorts the boxes by
-  // plan_dispatch3d's path: face boxes leave the list for the x-face kernel, the
-  // rest keep their order in the march launch (strips, or one thread per row for
-  // thin boxes). xface = 0 has no face boxes: the caller's list.
-  const Split3D sp = split_boxes3d(1, boxes, nboxes, tune);
+  // plan_launch3d runs split_boxes3d (kernel_select.cpp), which checks tune.xface
+  // and sorts the boxes by plan_dispatch3d's path: face boxes leave the list for
+  // the x-face kernel, the rest keep their order in the march launch (strips, or
+  // one thread per row for thin boxes). xface = 0 has no face boxes: the caller's
+  // list. With a signal it also checks signal_boxes and the tuning, and no box
+  // takes the face path.
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
-  // 32 planes per task (measured, profiles/diffusion3d.md: 3-8 % ahead of 128
-  // at 1024^3 and 1536^3, level at 512^3)
-  const int64_t total =
-      plan_boxes(L, sp.wide, sp.thin, sp.nwide, 1, V, tune.rows, tune.chunk_z, 32);
+  Split3D sp;
+  const Fused3DPlan plan =
+      plan_launch3d(L, sp, 1, V, boxes, nboxes, tune, tune.signal != nullptr, tune.signal_boxes);
+  const int64_t total = plan.blocks;
   if (L.n == 0 && !sp.faces()) return;
   const dim3 grid = grid_of(total), block(kBlock);
   hipStream_t s = as_stream(stream);
@@ -348,18 +364,64 @@ void stencil3d_boxes_gpu(double* T2, const double* T, const double* iCp, int64_t
       RMA_HIP_LAUNCH_CHECK();
     });
     if (L.n == 0) return;  // face boxes only: checked above
+    if (tune.signal) {  // the shipped tuning (plan_launch3d), the prefix blocks first
+      with_value<1, 2>(V, [&](auto v) {
+        with_access3<true>(nt, tune.uniform, [&](auto nts, auto ntl, auto uni) {
+          constexpr bool Uni = decltype(uni)::value;
+          stencil3d_march_kernel<decltype(v)::value, kSigRows, kSigUnroll, decltype(nts)::value,
+                                 decltype(ntl)::value, Uni, A, true>
+              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, L, k, remap,
+                                      WaveSig{tune.signal, plan.prefix_blocks});
+        });
+      });
+      RMA_HIP_LAUNCH_CHECK();
+      return;
+    }
     with_value<1, 2>(V, [&](auto v) {
       with_rows_unroll(tune.rows, tune.unroll, [&](auto r, auto u) {
         with_access3<true>(nt, tune.uniform, [&](auto nts, auto ntl, auto uni) {
           constexpr bool Uni = decltype(uni)::value;
           stencil3d_march_kernel<decltype(v)::value, decltype(r)::value, decltype(u)::value,
                                  decltype(nts)::value, decltype(ntl)::value, Uni, A>
-              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, L, k, remap);
+              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, L, k, remap,
+                                      NoSig{});
         });
       });
     });
     RMA_HIP_LAUNCH_CHECK();
   });
+}
+
+Fused3DPlan stencil3d_fused_plan(int K, int V, const Box* boxes, int nboxes,
+                                 const Stencil3DTuning& tune, int signal_boxes, int64_t* map) {
+  RMA_CHECK_ARG(K == 1 || K == 2, "K=" << K << " steps per pass is not instantiated (1 or 2)");
+  RMA_CHECK_ARG(V == 1 || V == 2, "V=" << V << " cells per lane (1 or 2)");
+  RMA_CHECK_ARG(signal_boxes >= 0, "signal_boxes=" << signal_boxes);
+  // the launchers' tuning checks that the block lists depend on
+  if (K == 1) {
+    RMA_CHECK_ARG(stencil3d_has(tune.rows, tune.unroll),
+                  "rows=" << tune.rows << " unroll=" << tune.unroll
+                          << ": rows 2 or 4 with unroll 1 or 2, or rows 8 with unroll 1");
+    RMA_CHECK_ARG(tune.chunk_z >= 0, "chunk_z=" << tune.chunk_z);
+  } else {
+    RMA_CHECK_ARG(tune.tb_rows == 0 || stencil3dk_has_rows(tune.tb_rows),
+                  "tb_rows=" << tune.tb_rows << " (0: default, 2 or 4)");
+    RMA_CHECK_ARG(tune.tb_chunk_z >= 0, "tb_chunk_z=" << tune.tb_chunk_z);
+  }
+  BoxList L{};
+  Split3D sp;
+  const Fused3DPlan plan =
+      plan_launch3d(L, sp, K, V, boxes, nboxes, tune, signal_boxes > 0, signal_boxes);
+  if (map) {
+    const int remap = tune.xcd_remap ? 1 : 0;
+    for (int64_t b = 0; b < plan.blocks; ++b) {
+      // without a prefix this is locate_block's map: xcd_remap over the whole grid
+      const BlockAt at = block_after(L, b, plan.blocks, remap, plan.prefix_blocks);
+      map[2 * b] = at.bi;
+      map[2 * b + 1] = at.lb;
+    }
+  }
+  return plan;
 }
 
 }  // namespace rma

@@ -124,6 +124,57 @@ __device__ __forceinline__ BlockAt locate_block(const List& L, int remap) {
   return at;
 }
 
+// The same prologue for a signalling launch (Stencil3DTuning::signal): the first
+// `first` blocks, the signal prefix, keep dispatch order and the rest is XCD-
+// remapped among itself (xcd_remap_after). Block blk of nwg; the caller fills in
+// the wave. Host-callable: stencil3d_fused_plan maps every block with the
+// function the kernels run. Unsignalled kernels keep locate_block as it is.
+template <class List>
+__host__ __device__ __forceinline__ BlockAt block_after(const List& L, int64_t blk, int64_t nwg,
+                                                        int remap, int64_t first) {
+  const int64_t b = remap ? xcd_remap_after(blk, nwg, first) : blk;
+  BlockAt at;
+  at.wave = 0;
+  at.bi = 0;
+  while (at.bi < L.n - 1 && b >= L.block_end[at.bi]) ++at.bi;  // block-uniform, <= 8 steps
+  at.lb = b - (at.bi ? L.block_end[at.bi - 1] : 0);
+  return at;
+}
+
+// The trailing argument of the two march kernels, SigArg<Sig>: nothing (the
+// kernels as they were; NoSig is empty and the if constexpr (Sig) statements
+// vanish), or the signal words of a frame-first fused pass. The waves of these
+// kernels leave independently (no barrier; waves past the last band return at
+// once; thin-box threads return one by one), so every wave of every prefix
+// block counts itself (signal_wave_done): each way out of a signalling
+// instantiation calls wave_done() behind the wave's last store. Lane 0 counts;
+// where lanes leave one by one (the thin path) lane 0 has the lowest row of its
+// wave: the lanes that store run the same loop together with it, so its call is
+// behind every store of the wave, and a wave whose lane 0 has no row stores
+// nothing. The last of first * 4 waves re-arms the counter and raises the
+// flag with a system-scope release. first comes from plan_launch3d, as the grid.
+struct NoSig {};
+struct WaveSig {
+  uint64_t* sig;
+  int64_t first;  // blocks of the signal prefix
+  __device__ __forceinline__ void wave_done() const {
+    if ((int64_t)blockIdx.x < first) signal_wave_done(sig, first * kWavesPerBlock);
+  }
+};
+template <bool Sig>
+using SigArg = std::conditional_t<Sig, WaveSig, NoSig>;
+
+template <class List>
+__device__ __forceinline__ BlockAt locate_block(const List& L, int remap, NoSig) {
+  return locate_block(L, remap);
+}
+template <class List>
+__device__ __forceinline__ BlockAt locate_block(const List& L, int remap, const WaveSig& s) {
+  BlockAt at = block_after(L, (int64_t)blockIdx.x, (int64_t)gridDim.x, remap, s.first);
+  at.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  return at;
+}
+
 // Blocks of a strip-march launch of K steps per pass, V cells per lane and R
 // output rows per wave; thin[i] marks a thin box (plan_dispatch3d's kPathThin,
 // one-step only). Block lb of a box: strip fastest, then the group of 4 bands,
@@ -212,6 +263,62 @@ inline void check_tuning3d(const Stencil3DTuning& tune, const StencilCoef3& c, c
   RMA_CHECK_ARG(chunk_z >= 0, pre << "chunk_z=" << chunk_z);
   RMA_CHECK_ARG(!tune.fast_math || fast7_ok(c),
                 "fast_math: fast7 needs lam != 0 and finite coefficients");
+}
+
+// defaults of Stencil3DTuning::chunk_z = 0 (profiles/diffusion3d.md: 32 planes per
+// task measured 3-8 % ahead of 128 at 1024^3 and 1536^3, level at 512^3) and of
+// tb_rows / tb_chunk_z = 0 (profiles/diffusion3d_temporal.md)
+constexpr int64_t kDefaultChunkZ = 32;
+constexpr int kTbDefaultRows = 4;
+constexpr int64_t kTbDefaultChunkZ = 32;
+// the tuning the signalling kernels are instantiated for: the shipped one
+constexpr int kSigRows = 4, kSigUnroll = 2;
+
+// The march launch of a K-step pass (K = 1, 2) at V cells per lane: the box lists
+// (sp, L) and the block counts, the one function both launchers and
+// stencil3d_fused_plan run. signalling (Stencil3DTuning::signal set, or a plan
+// asked for with signal_boxes > 0): the first signal_boxes non-empty boxes are the
+// signal prefix, every box runs the march or thin path (xface is checked and then
+// not applied) and the tuning must be the shipped one. Every refusal names its
+// argument and comes before any work.
+inline Fused3DPlan plan_launch3d(BoxList& L, Split3D& sp, int K, int V, const Box* boxes,
+                                 int nboxes, const Stencil3DTuning& tune, bool signalling,
+                                 int signal_boxes) {
+  const int R = K == 1 ? tune.rows : (tune.tb_rows > 0 ? tune.tb_rows : kTbDefaultRows);
+  Stencil3DTuning t = tune;
+  if (signalling) {
+    RMA_CHECK_ARG(tune.xface >= 0 && tune.xface <= kXfaceMax,
+                  "xface=" << tune.xface << " (0: off, or the widest face box, up to "
+                           << kXfaceMax << ")");
+    t.xface = 0;
+    if (K == 1)
+      RMA_CHECK_ARG(tune.rows == kSigRows && tune.unroll == kSigUnroll,
+                    "signal: rows=" << tune.rows << " unroll=" << tune.unroll
+                                    << " (signalling launches are instantiated for rows="
+                                    << kSigRows << " unroll=" << kSigUnroll << " only)");
+    else
+      RMA_CHECK_ARG(R == kTbDefaultRows,
+                    "signal: tb_rows=" << tune.tb_rows
+                                       << " (signalling launches are instantiated for tb_rows="
+                                       << kTbDefaultRows << ", the default, only)");
+  } else {
+    RMA_CHECK_ARG(signal_boxes == 0, "signal is null with signal_boxes=" << signal_boxes);
+  }
+  sp = split_boxes3d(K, boxes, nboxes, t);
+  if (signalling)
+    RMA_CHECK_ARG(signal_boxes >= 1 && signal_boxes < sp.nwide,
+                  "signal_boxes=" << signal_boxes << " (1 .. " << sp.nwide - 1
+                                  << ": a prefix of the " << sp.nwide
+                                  << " non-empty boxes with at least one box after it)");
+  Fused3DPlan p;
+  p.blocks = K == 1 ? plan_boxes(L, sp.wide, sp.thin, sp.nwide, 1, V, R, tune.chunk_z,
+                                 kDefaultChunkZ)
+                    : plan_boxes(L, sp.wide, sp.thin, sp.nwide, K, V, R, tune.tb_chunk_z,
+                                 kTbDefaultChunkZ);
+  p.boxes = L.n;
+  p.prefix_blocks = signalling ? L.block_end[signal_boxes - 1] : 0;
+  p.signalling_waves = p.prefix_blocks * kWavesPerBlock;
+  return p;
 }
 
 // ---------------------------------------------------------------------------

@@ -65,20 +65,22 @@ namespace rma {
 namespace {
 using namespace march;
 
-// defaults of Stencil3DTuning::tb_rows / tb_chunk_z = 0 (profiles/diffusion3d_temporal.md)
-constexpr int kTbDefaultRows = 4;
-constexpr int64_t kTbDefaultChunkZ = 32;
-
-template <int K, int V, int R, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3>
+// Sig (Stencil3DTuning::signal, frame-first fused passes; stencil3d_device.h
+// SigArg): the blocks of the signal prefix keep dispatch order and each way out of
+// the kernel counts the wave. Instantiated for R = kTbDefaultRows only. Without
+// Sig sg is empty and this is the kernel it was: the 48 instantiations above keep
+// their registers, scratch and occupancy (profiles/diffusion3d_fused.md).
+template <int K, int V, int R, bool NTS, bool NTL, bool Uni = false, int A = kCanonical3,
+          bool Sig = false>
 __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict__ T2,
                                                               const double* __restrict__ T,
                                                               Factor<Uni> iCp,
                                                               int64_t nx, int64_t ny, int64_t nz,
                                                               BoxList L, Coef3<A> k,
-                                                              int remap) {
+                                                              int remap, SigArg<Sig> sg) {
   constexpr int NR = R + 2 * K;                 // rows of the level-0 window
   constexpr int64_t kStep = kWave * V - 2 * (K - 1);  // strip advance
-  const auto [bi, lb, wave] = locate_block(L, remap);
+  const auto [bi, lb, wave] = locate_block(L, remap, sg);
   const Box box = L.b[bi];
   const int64_t plane = nx * ny;
   // block lb of a box: strip fastest, then the group of 4 bands, then the z chunk
@@ -86,7 +88,10 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
   const int64_t rest = lb / L.strips[bi];
   const int64_t band = (rest % L.groups[bi]) * kWavesPerBlock + wave;
   const int64_t zc = rest / L.groups[bi];
-  if (band >= L.bands[bi]) return;  // the whole wave
+  if (band >= L.bands[bi]) {  // the whole wave
+    if constexpr (Sig) sg.wave_done();
+    return;
+  }
   const int64_t xs = L.xa[bi] + strip * kStep;
   const int64_t ya = box.y0 + band * R;
   const int64_t za = box.z0 + zc * L.chunk_z[bi];
@@ -202,6 +207,7 @@ __global__ __launch_bounds__(kBlock) void stencil3d_tb_kernel(double* __restrict
           for (int v = 0; v < V; ++v) ic[l][j][v] = ic[l - 1][j][v];
     }
   }
+  if constexpr (Sig) sg.wave_done();
 }
 
 // ---------------------------------------------------------------------------
@@ -398,16 +404,19 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
   const int R = tune.tb_rows > 0 ? tune.tb_rows : kTbDefaultRows;
   RMA_CHECK_ARG(stencil3dk_has_rows(R), "tb_rows=" << tune.tb_rows << " (0: default, 2 or 4)");
   check_tuning3d(tune, c, "tb_", tune.tb_nontemporal, tune.tb_chunk_z);
-  // split_boxes3d (kernel_select.cpp) checks tune.xface and sorts the boxes by
-  // plan_dispatch3d's path: face boxes leave the list for the x-face kernel,
-  // launched first on the same stream, the rest keep their order in the strip
-  // march. xface = 0 has no face boxes: the caller's list, launch for launch.
-  const Split3D sp = split_boxes3d(K, boxes, nboxes, tune);
+  // plan_launch3d runs split_boxes3d (kernel_select.cpp), which checks tune.xface
+  // and sorts the boxes by plan_dispatch3d's path: face boxes leave the list for
+  // the x-face kernel, launched first on the same stream, the rest keep their
+  // order in the strip march. xface = 0 has no face boxes: the caller's list,
+  // launch for launch. With a signal it also checks signal_boxes and tb_rows, and
+  // no box takes the face path.
   const int Rf = tune.tb_rows > 0 ? tune.tb_rows : kTbFaceDefaultRows;
   const int V = stencil3d_vec(T2, T, iCp, nx, tune);
   BoxList L{};
-  const int64_t total =
-      plan_boxes(L, sp.wide, sp.thin, sp.nwide, K, V, R, tune.tb_chunk_z, kTbDefaultChunkZ);
+  Split3D sp;
+  const Fused3DPlan plan =
+      plan_launch3d(L, sp, K, V, boxes, nboxes, tune, tune.signal != nullptr, tune.signal_boxes);
+  const int64_t total = plan.blocks;
   if (L.n == 0 && !sp.faces()) return;
   const dim3 grid = grid_of(total), block(kBlock);
   hipStream_t s = as_stream(stream);
@@ -430,13 +439,27 @@ void stencil3dk_boxes_gpu(int K, double* T2, const double* T, const double* iCp,
       RMA_HIP_LAUNCH_CHECK();
     });
     if (L.n == 0) return;  // face boxes only: checked above
+    if (tune.signal) {  // the default rows (plan_launch3d), the prefix blocks first
+      with_value<1, 2>(V, [&](auto v) {
+        with_access3<true>(nt, tune.uniform, [&](auto nts, auto ntl, auto uni) {
+          constexpr bool Uni = decltype(uni)::value;
+          stencil3d_tb_kernel<2, decltype(v)::value, kTbDefaultRows, decltype(nts)::value,
+                              decltype(ntl)::value, Uni, A, true>
+              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, nz, L, k, remap,
+                                      WaveSig{tune.signal, plan.prefix_blocks});
+        });
+      });
+      RMA_HIP_LAUNCH_CHECK();
+      return;
+    }
     with_value<1, 2>(V, [&](auto v) {
       with_value<2, 4>(R, [&](auto r) {
         with_access3<true>(nt, tune.uniform, [&](auto nts, auto ntl, auto uni) {
           constexpr bool Uni = decltype(uni)::value;
           stencil3d_tb_kernel<2, decltype(v)::value, decltype(r)::value, decltype(nts)::value,
                               decltype(ntl)::value, Uni, A>
-              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, nz, L, k, remap);
+              <<<grid, block, 0, s>>>(T2, T, factor_arg<Uni>(iCp, fac), nx, ny, nz, L, k, remap,
+                                      NoSig{});
         });
       });
     });

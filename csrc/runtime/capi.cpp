@@ -430,6 +430,14 @@ int rma_executor3d_create(rma_grid* g, int mode, double* T, double* T2, const do
                           int64_t nx, int64_t ny, int64_t nz, const double coef[5],
                           const int64_t b_width[3], int steps_per_pass, int fast_math, int xface,
                           rma_executor3d** out) {
+  return rma_executor3d_create_f(g, mode, T, T2, iCp, nx, ny, nz, coef, b_width, steps_per_pass,
+                                 fast_math, xface, 0, out);
+}
+
+int rma_executor3d_create_f(rma_grid* g, int mode, double* T, double* T2, const double* iCp,
+                            int64_t nx, int64_t ny, int64_t nz, const double coef[5],
+                            const int64_t b_width[3], int steps_per_pass, int fast_math,
+                            int xface, int fused, rma_executor3d** out) {
   return guard([&] {
     RMA_CHECK_ARG(g != nullptr && out != nullptr && coef != nullptr, "grid, out or coef is NULL");
     RMA_CHECK_ARG(!g->finalized, "grid already finalized");
@@ -439,6 +447,7 @@ int rma_executor3d_create(rma_grid* g, int mode, double* T, double* T2, const do
     p.steps_per_pass = steps_per_pass;
     p.fast_math = fast_math ? 1 : 0;
     p.xface = xface;
+    p.fused = fused;
     for (int d = 0; d < 3; ++d) {
       if (b_width) p.b_width[d] = b_width[d];  // NULL: (16, 2, 2)
       p.overlaps[d] = g->overlaps[d];
@@ -459,7 +468,16 @@ int rma_executor3d_run(rma_executor3d* e, int64_t nsteps, void* stream) {
   });
 }
 
+int rma_executor3d_check(rma_executor3d* e) {
+  return guard([&] {
+    RMA_CHECK_ARG(e != nullptr, "executor is NULL");
+    e->ex->check();
+  });
+}
+
 int rma_executor3d_parity(const rma_executor3d* e) { return e->ex->parity(); }
+
+int64_t rma_executor3d_fused_passes(const rma_executor3d* e) { return e->ex->fused_passes(); }
 
 int rma_executor3d_uniform(const rma_executor3d* e) { return e->ex->uniform() ? 1 : 0; }
 

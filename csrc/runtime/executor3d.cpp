@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -43,6 +45,23 @@ Diffusion3DExecutor::Diffusion3DExecutor(double* T, double* T2, const double* iC
                 "xface " << p.xface << " (-1, or 0.." << kXfaceMax << ")");
   RMA_CHECK_ARG(!p.fast_math || fast7_ok(p.coef),
                 "fast_math: the fast7 arithmetic needs lam != 0 and finite coefficients");
+  RMA_CHECK_ARG(p.fused == 0 || p.fused == 1,
+                "fused " << p.fused << " (0 two launches, 1 frame-first single launch)");
+  RMA_CHECK_ARG(!p.fused || p.mode == 1, "fused " << p.fused << " needs mode 1 (perf_hide), got "
+                                                          << "mode " << p.mode);
+  // the signalling kernels exist for the shipped tuning only (plan_launch3d refuses
+  // the rest per launch; here it is refused once, before any work)
+  RMA_CHECK_ARG(!p.fused || (p.tune.rows == 4 && p.tune.unroll == 2 &&
+                             (p.tune.tb_rows == 0 || p.tune.tb_rows == 4)),
+                "fused 1 needs rows 4, unroll 2 and tb_rows 0 or 4, got rows "
+                    << p.tune.rows << ", unroll " << p.tune.unroll << ", tb_rows "
+                    << p.tune.tb_rows);
+  RMA_CHECK_ARG(p.fused_timeout_s > 0.0, "fused_timeout_s " << p.fused_timeout_s << " (> 0)");
+  // bounded wait of the exchange stream for the frame flag (seconds); the
+  // environment's value, where set, replaces the parameter, as in the 2D executor
+  fused_timeout_s_ = std::getenv("RMA_EXEC_FUSED_TIMEOUT")
+                         ? env_double("RMA_EXEC_FUSED_TIMEOUT", 60.0, 1e-9, 1e6)
+                         : p.fused_timeout_s;
   if (halo_) nbr_ = halo_->neighbors();
   for (int d = 0; d < 3; ++d) {
     if (nbr_[d][0] < 0 && nbr_[d][1] < 0) continue;
@@ -71,6 +90,18 @@ Diffusion3DExecutor::Diffusion3DExecutor(double* T, double* T2, const double* iC
       for (void** e : {&ev_in_, &ev_frame_, &ev_inner_, &ev_halo_})
         RMA_HIP_CHECK(
             hipEventCreateWithFlags(reinterpret_cast<hipEvent_t*>(e), hipEventDisableTiming));
+      if (p_.fused) {
+        RMA_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&sig_), 2 * sizeof(uint64_t)));
+        // zeroed on the stream the signalling launches run on and waited for: a
+        // null-stream memset is not ordered before work on a non-blocking stream
+        RMA_HIP_CHECK(hipMemsetAsync(sig_, 0, 2 * sizeof(uint64_t), lo));
+        RMA_HIP_CHECK(hipStreamSynchronize(lo));
+        RMA_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ferr_host_), sizeof(uint32_t),
+                                    hipHostMallocMapped));
+        *ferr_host_ = 0;
+        RMA_HIP_CHECK(
+            hipHostGetDevicePointer(reinterpret_cast<void**>(&ferr_dev_), ferr_host_, 0));
+      }
     }
     scan_factor();
     // the pack buffers exist before the first run (no allocation inside it)
@@ -84,7 +115,25 @@ Diffusion3DExecutor::Diffusion3DExecutor(double* T, double* T2, const double* iC
   }
 }
 
-Diffusion3DExecutor::~Diffusion3DExecutor() { release(); }
+Diffusion3DExecutor::~Diffusion3DExecutor() {
+  // drain first: a timeout of the last run is known only then
+  if (s_hi_) (void)hipStreamSynchronize(S(s_hi_));
+  if (ferr_host_ && __atomic_load_n(ferr_host_, __ATOMIC_ACQUIRE) != 0)
+    std::fprintf(stderr,
+                 "rma: Diffusion3DExecutor: a fused pass's wait for the frame flag timed out "
+                 "after %g s (RMA_EXEC_FUSED_TIMEOUT); the halos of that pass are wrong\n",
+                 fused_timeout_s_);
+  release();
+}
+
+void Diffusion3DExecutor::check() const {
+  if (!ferr_host_) return;
+  const uint32_t e = __atomic_load_n(ferr_host_, __ATOMIC_ACQUIRE);
+  RMA_CHECK_ARG(e == 0, "frame-first fused pass: the exchange stream's wait for the frame flag "
+                        "timed out after "
+                            << fused_timeout_s_
+                            << " s (RMA_EXEC_FUSED_TIMEOUT); the halos of that pass are wrong");
+}
 
 void Diffusion3DExecutor::release() {
   // work of the last run may still be queued on the two streams
@@ -97,6 +146,11 @@ void Diffusion3DExecutor::release() {
   if (s_hi_) (void)hipStreamDestroy(S(s_hi_));
   if (s_lo_) (void)hipStreamDestroy(S(s_lo_));
   s_hi_ = s_lo_ = nullptr;
+  // the streams' flag kernels and launches are drained: the words can go
+  if (sig_) (void)hipFree(sig_);
+  if (ferr_host_) (void)hipHostFree(ferr_host_);
+  sig_ = nullptr;
+  ferr_host_ = ferr_dev_ = nullptr;
 }
 
 void Diffusion3DExecutor::scan_factor() {
@@ -159,7 +213,7 @@ void Diffusion3DExecutor::exchange(double* A, stream_t s) {
 }
 
 void Diffusion3DExecutor::launch(int K, const Box* boxes, int n, bool frame, double* Tin,
-                                 double* Tout, stream_t s) const {
+                                 double* Tout, stream_t s, int signal_boxes) const {
   Box b[kMaxBoxes];
   int m = 0;
   for (int i = 0; i < n; ++i)
@@ -170,6 +224,11 @@ void Diffusion3DExecutor::launch(int K, const Box* boxes, int n, bool frame, dou
   tn.uniform = uniform_;
   tn.uniform_value = uniform_ ? c0_ : 0.0;
   tn.xface = frame ? xface_ : 0;  // one- and two-step frames (plan_dispatch3d caps the width)
+  if (signal_boxes > 0) {  // a fused pass: the first boxes are the signal prefix, no face path
+    tn.signal = sig_;
+    tn.signal_boxes = signal_boxes;
+    tn.xface = 0;
+  }
   if (K == 1)
     stencil3d_boxes_gpu(Tout, Tin, iCp_, nx_, ny_, nz_, b, m, p_.coef, tn, s);
   else
@@ -177,6 +236,7 @@ void Diffusion3DExecutor::launch(int K, const Box* boxes, int n, bool frame, dou
 }
 
 void Diffusion3DExecutor::run(int64_t nsteps, stream_t caller) {
+  check();
   const std::vector<int> passes = plan(nsteps);
   if (passes.empty()) return;
   // the depths of this run: K and, with a remainder, 1
@@ -219,6 +279,28 @@ void Diffusion3DExecutor::run(int64_t nsteps, stream_t caller) {
         launch(k, boxes, n, false, Tin, Tout, cur);
         exchange(Tout, cur);
       }
+    } else if (p_.fused) {
+      // Frame-first single launch (rma/executor3d.h). ev_frame_ is the event of
+      // H's previous exchange here (the unsplit pass above records it there too):
+      // the frame blocks read the halo. The launch follows the previous one on L
+      // in stream order, which covers what the frame of a split pass waits for.
+      const HideBoxes3& sp = split[k];
+      Box b[kMaxBoxes];
+      int m = 0;
+      for (const Box& f : sp.frame)
+        if (!f.empty()) b[m++] = f;
+      const int nframe = m;
+      b[m++] = sp.interior;
+      RMA_HIP_CHECK(hipStreamWaitEvent(L, E(ev_frame_), 0));
+      launch(k, b, m, false, Tin, Tout, L, nframe);
+      RMA_HIP_CHECK(hipEventRecord(E(ev_inner_), L));
+      // exchange stream: the frame flag (bounded wait), lowered for the next pass;
+      // the launch it waits on is already enqueued
+      flag_wait_gpu(sig_ + 1, 1, fused_timeout_s_, ferr_dev_, 1, H);
+      flag_write_gpu(sig_ + 1, 0, H);
+      exchange(Tout, H);
+      RMA_HIP_CHECK(hipEventRecord(E(ev_frame_), H));
+      ++fused_passes_;
     } else {
       const HideBoxes3& sp = split[k];
       // interior of the pass before: the frame reads its cells and overwrites

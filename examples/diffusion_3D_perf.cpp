@@ -4,9 +4,11 @@
 // time loop, barrier timers.
 //
 //   ./build/examples/diffusion_3D_perf [nx] [nt] [periodic] [steps_per_pass] [fast_math] [hide]
+//                                      [fused]
 //   (nx: cube edge, halo included; periodic 1: the rank is its own neighbour on
 //    all six sides; steps_per_pass 1 or 2; fast_math 1: the fast7 arithmetic;
-//    hide 1: perf_hide with b_width (16, 2, 2), 0: perf)
+//    hide 1: perf_hide with b_width (16, 2, 2), 0: perf; fused 1 (with hide 1):
+//    frame-first single-launch passes)
 //
 // Prints the reference line with T_eff = 3*nx*ny*nz*8 B / t_it. The first
 // min(10, nt - 1) steps are untimed, as in the reference scripts.
@@ -41,9 +43,10 @@ int main(int argc, char** argv) {
   const int K = argc > 4 ? std::atoi(argv[4]) : 1;
   const int fast = argc > 5 ? std::atoi(argv[5]) : 0;
   const int hide = argc > 6 ? std::atoi(argv[6]) : 0;
+  const int fused = argc > 7 ? std::atoi(argv[7]) : 0;
   if (n < 3 || nt < 1 || (K != 1 && K != 2)) {
     std::fprintf(stderr, "usage: %s [nx >= 3] [nt >= 1] [periodic 0|1] [steps_per_pass 1|2] "
-                         "[fast_math 0|1] [hide 0|1]\n", argv[0]);
+                         "[fast_math 0|1] [hide 0|1] [fused 0|1]\n", argv[0]);
     return 2;
   }
   HK(hipSetDevice(0));
@@ -73,11 +76,12 @@ int main(int argc, char** argv) {
   HK(hipStreamSynchronize(s));
   rma_executor3d* ex = nullptr;
   const int64_t b_width[3] = {16, 2, 2};
-  CK(rma_executor3d_create(g, hide ? 1 : 0, T, T2, iCp, n, n, n, coef, b_width, K, fast, 0, &ex));
+  CK(rma_executor3d_create_f(g, hide ? 1 : 0, T, T2, iCp, n, n, n, coef, b_width, K, fast, 0,
+                             fused, &ex));
   std::printf("Global grid: %ldx%ldx%ld (nprocs: 1, dims: %dx%dx%d)\n", (long)rma_nx_g(g),
               (long)rma_ny_g(g), (long)rma_nz_g(g), dims[0], dims[1], dims[2]);
-  std::printf("[loop] native %s, %d step(s) per pass, %s, 1/Cp %s\n", hide ? "perf_hide" : "perf",
-              K, fast ? "fast7" : "canonical",
+  std::printf("[loop] native %s%s, %d step(s) per pass, %s, 1/Cp %s\n",
+              hide ? "perf_hide" : "perf", fused ? " fused" : "", K, fast ? "fast7" : "canonical",
               rma_executor3d_uniform(ex) ? "uniform (kernel argument)" : "read per cell");
   const int warm = nt > 1 ? std::min(10, nt - 1) : 0;
   if (warm) CK(rma_executor3d_run(ex, warm, s));
@@ -93,6 +97,9 @@ int main(int argc, char** argv) {
   double c = 0;
   HK(hipMemcpy(&c, cur + ((n / 2) * n + n / 2) * n + n / 2, sizeof c, hipMemcpyDeviceToHost));
   std::printf("T[centre] = %.17g\n", c);
+  CK(rma_executor3d_check(ex));  // a fused pass's wait that timed out
+  if (fused)
+    std::printf("[hide] %lld fused passes\n", (long long)rma_executor3d_fused_passes(ex));
   CK(rma_executor3d_destroy(ex));
   HK(hipFree(T));
   HK(hipFree(T2));

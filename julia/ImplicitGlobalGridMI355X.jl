@@ -279,17 +279,19 @@ end
 # steps_per_pass = 1 or 2; b_width = perf_hide's boundary width per dimension from the
 # array edge; xface = 0..32 (the widest frame box on the x-face path of the one- and
 # two-step kernels, two-step frames up to width 30; -1: min(max(b_width[1], overlap_x), 32)).
+# fused = true (mode 1): frame-first single-launch passes (rma_executor3d_create_f), the
+# same field bit for bit; check_fused(ex) after synchronising throws if a wait timed out.
 # T2 must hold a copy of T.
 function Diffusion3DExecutor(T, T2, iCp, coef::NTuple{5,Float64}; mode::Integer=1,
                              steps_per_pass::Integer=1, b_width=(16, 2, 2),
-                             fast_math::Bool=false, xface::Integer=0)
+                             fast_math::Bool=false, xface::Integer=0, fused::Bool=false)
     out = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall(sym(:rma_executor3d_create), Cint,
+    check(ccall(sym(:rma_executor3d_create_f), Cint,
                 (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64,
-                 Ptr{Float64}, Ptr{Int64}, Cint, Cint, Cint, Ptr{Ptr{Cvoid}}),
+                 Ptr{Float64}, Ptr{Int64}, Cint, Cint, Cint, Cint, Ptr{Ptr{Cvoid}}),
                 GRID[], mode, devptr(T), devptr(T2), devptr(iCp), size(T, 1), size(T, 2),
                 size(T, 3), collect(coef), Int64[b_width...], steps_per_pass, Cint(fast_math),
-                xface, out))
+                xface, Cint(fused), out))
     ex = Diffusion3DExecutor(out[], T, T2, iCp)
     # pins the native grid like the 2D executor: any finalization order is safe
     finalizer(e -> ccall(sym(:rma_executor3d_destroy), Cint, (Ptr{Cvoid},), e.ptr), ex)
@@ -298,6 +300,13 @@ end
 
 run!(ex::Diffusion3DExecutor, n::Integer; stream::Ptr{Cvoid}=C_NULL) =
     check(ccall(sym(:rma_executor3d_run), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}), ex.ptr, n, stream))
+
+# after synchronising the stream: throws if a fused pass timed out waiting for its frame
+# flag (rma_executor3d_check); returns the fused-pass count
+function check_fused(ex::Diffusion3DExecutor)
+    check(ccall(sym(:rma_executor3d_check), Cint, (Ptr{Cvoid},), ex.ptr))
+    return ccall(sym(:rma_executor3d_fused_passes), Int64, (Ptr{Cvoid},), ex.ptr)
+end
 
 current_field(ex::Diffusion3DExecutor) =
     ccall(sym(:rma_executor3d_parity), Cint, (Ptr{Cvoid},), ex.ptr) == 0 ? ex.T : ex.T2

@@ -37,6 +37,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--xface", type=int, default=0,
                     help="perf_hide: widest frame box on the kernels' x-face path, one- and "
                          "two-step passes (0: off, -1: the x boundary width)")
+    ap.add_argument("--fused", action="store_true",
+                    help="perf_hide: frame-first single-launch passes (the frame boxes dispatch "
+                         "first in one launch with the interior; a device flag starts the "
+                         "exchange); bitwise the same field")
     ap.add_argument("--device", default=None, help="cpu, cuda, cuda:N (default: one GPU per rank)")
     ap.add_argument("--transport", default=os.environ.get("RMA_TRANSPORT", "auto"),
                     choices=["auto", "rccl", "ipc", "staged", "gloo", "self"])
@@ -130,9 +134,13 @@ def hide_line(model) -> str:
         own = model.owned_box(k)
         vol = lambda b: (b[1] - b[0]) * (b[3] - b[2]) * (b[5] - b[4])  # noqa: E731
         share = sum(vol(b) for b in frame) / max(1, vol(own))
-        path = face_path_text(model, k, frame)
-        overlap = ("frame + exchange overlap the interior" if frame and inner is not None
-                   and model.device.type == "cuda" else
+        splits = bool(frame) and inner is not None and model.device.type == "cuda"
+        # a fused launch has no box on the x-face path (the face kernels do not signal)
+        path = ("no box on the x-face path (fused launch)" if splits and cfg.fused
+                else face_path_text(model, k, frame))
+        overlap = ("fused: one launch, frame blocks first, the exchange behind their flag"
+                   if splits and cfg.fused else
+                   "split: frame + exchange overlap the interior, two launches" if splits else
                    "boxes in sequence: frame, exchange, interior" if frame and inner is not None
                    else "no overlap: one launch, then the exchange")
         parts.append(f"{k}-step passes: frame {frame}, inner {inner}, {100.0 * share:.1f} % of "
@@ -194,7 +202,7 @@ def main(argv=None) -> int:
                             device=a.device, check_every=a.check_every, temporal=a.temporal,
                             uniform_factor=a.uniform_factor, fast_math=a.fast_math,
                             b_width=a.b_width, xface=None if a.xface < 0 else a.xface,
-                            native=a.native)
+                            native=a.native, fused=a.fused)
     model = Diffusion3D(cfg)
     if model.g.me == 0:
         print(loop_line(model), flush=True)

@@ -81,6 +81,24 @@ It applies to the frame launch of one- and two-step passes alike; in a two-step
 pass a box needs two more columns than its width, so boxes wider than 30 keep
 the strip march (``ops.stencil3d_dispatch`` tells which box runs where).
 
+``fused`` (perf_hide only; the default is decided by profiles/diffusion3d_fused.md):
+frame-first single-launch passes. A pass that splits is ONE launch on L, the
+frame boxes as its signal prefix and the interior box after them
+(``Stencil3DTuning.signal``): the frame blocks dispatch first and the last frame
+wave raises a device flag. Per pass, enqueued in this order:
+
+1. L waits for the event of H's previous exchange (the frame blocks read the halo);
+2. the launch on L;
+3. on H ``flag_wait(signal + 1, 1)``, ``flag_write(signal + 1, 0)``,
+   ``update_halo_(T2)``, its event; then the buffers swap.
+
+The launch is always enqueued before the wait on it. No box of such a launch takes
+the x-face path. Passes that do not split stay the perf pass, ordered as above;
+CPU tensors run frame, exchange, interior in sequence as without ``fused``. The
+wait is bounded (``fused_timeout_s``, ``RMA_EXEC_FUSED_TIMEOUT``): ``synchronize()``
+raises if one timed out, since the halos of that pass are wrong. ``fused_passes``
+counts the fused passes. Bitwise the ``perf`` field.
+
 ``native`` (off by default; perf and perf_hide on a GPU whose grid has a native
 halo engine: the self, rccl, ipc and loopback transports): ``step(n)`` is one call
 into the C++ time loop (csrc/runtime/executor3d.cpp), which enqueues on the
@@ -91,12 +109,13 @@ tensors, ``ap`` and the other transports keep the Python-issued loop
 cost of both loops.
 
 Out of scope here (the 2D model has them): passes deeper than two steps, a pass
-planner, hipGraph replay, frame-first fused single-launch passes, checkpointing
-and direct-store halos.
+planner, hipGraph replay, checkpointing, direct-store halos and the x-face path
+inside a fused launch.
 """
 from __future__ import annotations
 
 import dataclasses
+import os
 from dataclasses import dataclass
 
 import torch
@@ -154,6 +173,11 @@ class Diffusion3DConfig:
     # C++ time loop (_C.Executor3D, csrc/runtime/executor3d.cpp) instead of pass by
     # pass from Python; bitwise the same field (profiles/diffusion3d_native.md)
     native: bool = False
+    # perf_hide: frame-first single-launch passes (module docstring); off by the rule
+    # of profiles/diffusion3d_fused.md. The wait of the exchange stream for the
+    # frame flag gives up after fused_timeout_s (RMA_EXEC_FUSED_TIMEOUT replaces it)
+    fused: bool = False
+    fused_timeout_s: float = 60.0
 
     def validate(self) -> None:
         if self.variant not in VARIANTS3D:
@@ -170,6 +194,12 @@ class Diffusion3DConfig:
             raise ValueError("temporal blocking applies to the perf variant (and perf_hide)")
         if self.fast_math and self.variant not in _KERNEL_VARIANTS:
             raise ValueError("fast_math applies to the perf variant (and perf_hide)")
+        if self.fused not in (False, True, 0, 1):
+            raise ValueError(f"fused must be False or True, got {self.fused!r}")
+        if self.fused and self.variant != "perf_hide":
+            raise ValueError(f"fused=True applies to the perf_hide variant, got {self.variant!r}")
+        if self.fused and not float(self.fused_timeout_s) > 0.0:
+            raise ValueError(f"fused_timeout_s > 0 required, got {self.fused_timeout_s}")
         if self.variant == "perf_hide":
             bw = tuple(self.b_width)
             if len(bw) != 3 or any(int(b) != b or b < 1 for b in bw):
@@ -228,6 +258,8 @@ class Diffusion3D:
         self.init_field(self.T)
         self.T2 = self.T.clone() if cfg.variant in _KERNEL_VARIANTS else None
         self._hide = None  # perf_hide on a GPU: (H, L, events), created at the first step
+        self._fused = None  # cfg.fused on a GPU: (signal words, error word), with _hide
+        self._fused_passes = 0
         if cfg.variant == "ap":  # flux arrays of the interior rows, preallocated
             self.qx = torch.empty((nz - 2, ny - 2, nx - 1), **f64)
             self.qy = torch.empty((nz - 2, ny - 1, nx - 2), **f64)
@@ -257,9 +289,10 @@ class Diffusion3D:
 
         cfg, g = self.cfg, self.g
         tn = cfg.tuning or ops.Stencil3DTuning()
-        if tn.uniform or tn.fast_math or tn.xface:
-            raise ValueError("native=True sets uniform, fast_math and xface per launch from the "
-                             "config (uniform_factor, fast_math, xface), not from cfg.tuning")
+        if tn.uniform or tn.fast_math or tn.xface or tn.signal or tn.signal_boxes:
+            raise ValueError("native=True sets uniform, fast_math, xface and the signal per launch "
+                             "from the config (uniform_factor, fast_math, xface, fused), not from "
+                             "cfg.tuning")
         self._bufs = (self.T, self.T2)
         self._exec = native().Executor3D(
             self.T.data_ptr(), self.T2.data_ptr(), self.iCp.data_ptr(), cfg.nx, cfg.ny, cfg.nz,
@@ -271,7 +304,8 @@ class Diffusion3D:
             uniform_factor=bool(cfg.uniform_factor), rows=int(tn.rows), unroll=int(tn.unroll),
             vec=int(tn.vec), nontemporal=int(tn.nontemporal), chunk_z=int(tn.chunk_z),
             xcd_remap=int(tn.xcd_remap), tb_rows=int(tn.tb_rows), tb_chunk_z=int(tn.tb_chunk_z),
-            tb_nontemporal=int(tn.tb_nontemporal))
+            tb_nontemporal=int(tn.tb_nontemporal), fused=1 if cfg.fused else 0,
+            fused_timeout_s=float(cfg.fused_timeout_s))
         self._adopt_verdict()
 
     def _adopt_verdict(self) -> None:
@@ -415,11 +449,38 @@ class Diffusion3D:
             xf = min(max(int(self.cfg.b_width[0]), int(self.g.overlaps[0])), ops.XFACE_MAX)
         return int(xf)
 
-    def _launch(self, k: int, boxes, frame: bool = False) -> None:
-        """One k-step launch T -> T2 on the boxes, on the current stream."""
+    @property
+    def fused_passes(self) -> int:
+        """Passes enqueued as one frame-first launch so far (cfg.fused on a GPU)."""
+        if self._exec is not None:
+            return int(self._exec.fused_passes)
+        return self._fused_passes
+
+    def fused_timeout(self) -> float:
+        """Bound of the exchange stream's wait for the frame flag, seconds:
+        RMA_EXEC_FUSED_TIMEOUT where set (as the native loops read it), else
+        cfg.fused_timeout_s."""
+        v = os.environ.get("RMA_EXEC_FUSED_TIMEOUT")
+        if v is None:
+            return float(self.cfg.fused_timeout_s)
+        try:
+            t = float(v)
+        except ValueError:
+            t = float("nan")
+        if not 1e-9 <= t <= 1e6:
+            raise ValueError(f"RMA_EXEC_FUSED_TIMEOUT={v!r} (a number of seconds in [1e-9, 1e6])")
+        return t
+
+    def _launch(self, k: int, boxes, frame: bool = False, signal_boxes: int = 0) -> None:
+        """One k-step launch T -> T2 on the boxes, on the current stream; with
+        signal_boxes the first boxes are the signal prefix of a fused pass."""
         tn = self._tuning(k)
         if frame and self.frame_xface(k):
             tn = dataclasses.replace(tn or ops.Stencil3DTuning(), xface=self.frame_xface(k))
+        if signal_boxes:
+            tn = dataclasses.replace(tn or ops.Stencil3DTuning(), xface=0,
+                                     signal=self._fused[0].data_ptr(),
+                                     signal_boxes=int(signal_boxes))
         if k == 1:
             ops.stencil3d_step(self.T2, self.T, self.iCp, self.coef, boxes, tuning=tn)
         else:
@@ -439,6 +500,14 @@ class Diffusion3D:
                               torch.cuda.Stream(self.device, priority=0),
                               [torch.cuda.Event() for _ in range(4)])
             H, L, (ev_in, ev_frame, ev_inner, ev_halo) = self._hide
+            if self.cfg.fused and self._fused is None:
+                # [frame wave counter, frame flag] and the error word of the bounded
+                # wait, zeroed on L, where the signalling launches run, and waited for
+                with torch.cuda.stream(L):
+                    self._fused = (torch.zeros(2, dtype=torch.int64, device=self.device),
+                                   torch.zeros(1, dtype=torch.int32, device=self.device))
+                L.synchronize()
+                self._fused_timeout = self.fused_timeout()
             cur = torch.cuda.current_stream(self.device)
             ev_in.record(cur)
             H.wait_event(ev_in)
@@ -467,6 +536,24 @@ class Diffusion3D:
                 update_halo_(self.T2)
                 self._launch(k, [inner])
                 self.T, self.T2 = self.T2, self.T
+            elif self.cfg.fused:
+                from .._native import native
+
+                # frame-first single launch (module docstring); ev_frame is the event
+                # of H's previous exchange here
+                sig, err = self._fused
+                L.wait_event(ev_frame)
+                with torch.cuda.stream(L):
+                    self._launch(k, list(frame) + [inner], signal_boxes=len(frame))
+                ev_inner.record(L)
+                native().flag_wait(sig.data_ptr() + 8, 1, self._fused_timeout, err.data_ptr(), 1,
+                                   H.cuda_stream)
+                native().flag_write(sig.data_ptr() + 8, 0, H.cuda_stream)
+                with torch.cuda.stream(H):
+                    update_halo_(self.T2)
+                ev_frame.record(H)
+                self.T, self.T2 = self.T2, self.T
+                self._fused_passes += 1
             else:
                 H.wait_event(ev_inner)  # interior of the pass before: reads / writes above
                 with torch.cuda.stream(H):
@@ -507,8 +594,16 @@ class Diffusion3D:
         update_halo_(T)
 
     def synchronize(self) -> None:
+        """Wait for the device; raises if a fused pass's wait for the frame flag
+        timed out (the halos of that pass are wrong)."""
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
+            if self._exec is not None:
+                self._exec.check()
+            elif self._fused is not None and int(self._fused[1].item()) != 0:
+                raise RuntimeError("frame-first fused pass: the exchange stream's wait for the "
+                                   f"frame flag timed out after {self._fused_timeout} s "
+                                   "(RMA_EXEC_FUSED_TIMEOUT); the halos of that pass are wrong")
 
     def check_finite(self) -> None:
         bad = float(ops.reduce(self.field, "nonfinite"))

@@ -8,7 +8,8 @@ from .stencil import (FAST5, KERNELS, KSTEP_CORE, LAB_KERNELS, PIPE, PIPE_MAX_K,
 from .stencil3d import (TB_ROWS_3D, TEMPORAL_3D, TUNINGS_3D, XFACE_MAX, Box, Stencil3DTuning, StencilCoef3,
                         TileGeometry3, init_gaussian3d_, init_random3d_, interior_box,
                         fast7_ok, stencil3d_step, stencil3d_torch, stencil3dk_step, stencil3dk_torch,
-                        hide_boxes3d, stencil3d_dispatch, validate_boxes)
+                        hide_boxes3d, stencil3d_dispatch, validate_boxes, FusedPlan3D,
+                        stencil3d_fused_plan)
 from .halo_ops import copy_plane, copy_planes
 from .block_ops import assemble_blocks, copy_blocks
 
@@ -22,5 +23,5 @@ __all__ = [
     "TUNINGS_3D", "Box", "Stencil3DTuning", "StencilCoef3", "TileGeometry3", "init_gaussian3d_",
     "init_random3d_", "interior_box", "stencil3d_step", "stencil3d_torch", "validate_boxes",
     "TB_ROWS_3D", "TEMPORAL_3D", "fast7_ok", "stencil3dk_step", "stencil3dk_torch",
-    "XFACE_MAX", "hide_boxes3d", "stencil3d_dispatch",
+    "XFACE_MAX", "hide_boxes3d", "stencil3d_dispatch", "FusedPlan3D", "stencil3d_fused_plan",
 ]

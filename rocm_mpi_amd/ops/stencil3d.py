@@ -78,7 +78,21 @@ class Stencil3DTuning:
     two-step march of one LX-column segment; a box of width W needs W + 2 <= LX,
     so boxes wider than ``min(xface, 30)`` keep the strip march. Bitwise the same
     result. ``stencil3d_dispatch`` tells which box takes which path. CPU tensors
-    accept and ignore it."""
+    accept and ignore it.
+
+    ``signal`` / ``signal_boxes`` (frame-first fused passes): ``signal`` is the
+    address of two device ``uint64`` words, a counter that is zero and a flag. The
+    blocks of the first ``signal_boxes`` non-empty boxes then dispatch first (never
+    XCD-remapped), every one of their waves counts itself in ``signal[0]`` after its
+    last store, and the last one resets the counter and stores 1 into ``signal[1]``
+    with a system-scope release: a ``flag_wait`` on another stream orders work after
+    those boxes without waiting for the rest of the launch. It needs
+    ``1 <= signal_boxes <`` the number of non-empty boxes and the shipped tuning
+    (``rows=4, unroll=2``; ``tb_rows`` 0 or 4). The x-face kernels do not signal: in
+    a signalling launch every box runs the march or thin path and ``xface`` is not
+    applied (``stencil3d_dispatch`` says so). ``stencil3d_fused_plan`` returns the
+    block counts of such a launch. Bitwise the unsignalled result; CPU tensors
+    accept and ignore both fields."""
 
     rows: int = 4
     unroll: int = 2
@@ -93,6 +107,8 @@ class Stencil3DTuning:
     uniform_value: float | None = None  # None: read iCp[0, 0, 0] (synchronises the device)
     fast_math: bool = False
     xface: int = 0
+    signal: int = 0  # address of the two signal words (0: no signal)
+    signal_boxes: int = 0
 
 
 XFACE_MAX = 32  # widest box the x-face path takes (Stencil3DTuning.xface)
@@ -281,7 +297,8 @@ def stencil3d_step(T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor, coef: S
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  int(tn.rows), int(tn.unroll), int(tn.vec), int(tn.nontemporal),
                                  int(tn.chunk_z), int(tn.xcd_remap), stream_handle(T), True,
-                                 *_uniform_args(tn, iCp), fast_math=fast, xface=xface)
+                                 *_uniform_args(tn, iCp), fast_math=fast, xface=xface,
+                                 signal=int(tn.signal), signal_boxes=int(tn.signal_boxes))
     elif has_native():
         native().stencil3d_boxes(_ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes, tuple(coef),
                                  4, 1, 2, 0, 0, 0, 0, False, fast_math=fast)
@@ -334,7 +351,8 @@ def stencil3dk_step(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor
                                   int(tn.nontemporal), int(tn.chunk_z), int(tn.xcd_remap),
                                   int(tn.tb_rows), int(tn.tb_chunk_z), int(tn.tb_nontemporal),
                                   stream_handle(T), True, *_uniform_args(tn, iCp),
-                                  fast_math=fast, xface=xface)
+                                  fast_math=fast, xface=xface, signal=int(tn.signal),
+                                  signal_boxes=int(tn.signal_boxes))
     elif has_native():
         native().stencil3dk_boxes(K, _ptr(T2), _ptr(T), _ptr(iCp), nx, ny, nz, boxes,
                                   tuple(coef), 4, 1, 2, 0, 0, 0, 0, 0, 0, 0, False,
@@ -351,7 +369,9 @@ def stencil3d_dispatch(K: int, shape: Sequence[int], boxes: Sequence[Box],
     ``"thin"`` (one-step boxes at most 8 wide, one thread per row, ``lanes`` 1)
     and ``"xface"`` (``tuning.xface``: ``lanes`` = 8, 16 or 32 per row). It is the
     host function both launchers run (``plan_dispatch3d``, csrc/kernels/
-    kernel_select.cpp), so it needs the native extension and no GPU."""
+    kernel_select.cpp), so it needs the native extension and no GPU. With
+    ``tuning.signal`` set (a frame-first fused launch) ``xface`` is not applied: no
+    box takes the ``"xface"`` path."""
     K = int(K)
     if K not in TEMPORAL_3D:
         raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
@@ -360,8 +380,50 @@ def stencil3d_dispatch(K: int, shape: Sequence[int], boxes: Sequence[Box],
         raise ValueError(f"xface={xface} (0: off, or the widest face box, up to {XFACE_MAX})")
     nz, ny, nx = (int(v) for v in shape)
     boxes = validate_boxes(boxes, nx, ny, nz)
+    if tuning is not None and tuning.signal:
+        xface = 0  # the x-face kernels do not signal
     got = native().stencil3d_dispatch(K, boxes, xface)
     return [(b, path, int(lanes)) for b, (path, lanes) in zip(boxes, got)]
+
+
+class FusedPlan3D(NamedTuple):
+    """``stencil3d_fused_plan``'s answer."""
+
+    blocks: int  # blocks of the march launch
+    prefix_blocks: int  # blocks of the signal prefix: the first ones, in dispatch order
+    signalling_waves: int  # waves that count in signal[0]: 4 per prefix block
+    boxes: list  # the boxes of the launch, in launch order
+    block_map: list  # per block: (index into boxes, block inside that box)
+
+
+def stencil3d_fused_plan(K: int, shape: Sequence[int], boxes: Sequence[Box], signal_boxes: int,
+                         tuning: Stencil3DTuning | None = None) -> FusedPlan3D:
+    """The march launch of a K-step GPU pass on a ``(nz, ny, nx)`` field whose first
+    ``signal_boxes`` non-empty boxes are the signal prefix (``Stencil3DTuning.signal``):
+    its block counts and the ``(box, block inside the box)`` every block works on,
+    computed on the host by the functions the launchers and the kernels run
+    (``stencil3d_fused_plan``, csrc/kernels/stencil3d.hip): the native extension, no
+    GPU. Every refusal of a signalling launch is raised here too. ``signal_boxes=0``
+    plans the unsignalled launch (``tuning.xface`` applies; boxes on the x-face path
+    are not part of the march launch). Cells per lane are ``tuning.vec`` for even
+    ``nx`` (16-byte aligned arrays assumed), else 1."""
+    K = int(K)
+    if K not in TEMPORAL_3D:
+        raise ValueError(f"K={K} steps per pass is not instantiated (one of {TEMPORAL_3D})")
+    tn = tuning or Stencil3DTuning()
+    nz, ny, nx = (int(v) for v in shape)
+    boxes = validate_boxes(boxes, nx, ny, nz)
+    V = int(tn.vec) if nx % 2 == 0 else 1
+    blocks, prefix, waves, _, pairs = native().stencil3d_fused_plan(
+        K, V, boxes, int(signal_boxes), rows=int(tn.rows), unroll=int(tn.unroll),
+        chunk_z=int(tn.chunk_z), xcd_remap=int(tn.xcd_remap), tb_rows=int(tn.tb_rows),
+        tb_chunk_z=int(tn.tb_chunk_z), xface=int(tn.xface))
+    if int(signal_boxes) > 0:
+        used = boxes
+    else:
+        used = [b for b, path, _ in stencil3d_dispatch(K, shape, boxes, tn) if path != "xface"]
+    return FusedPlan3D(int(blocks), int(prefix), int(waves), used,
+                       [(int(a), int(b)) for a, b in pairs])
 
 
 def stencil3dk_torch(K: int, T2: torch.Tensor, T: torch.Tensor, iCp: torch.Tensor,
